@@ -12,6 +12,14 @@ worlds (weak scaling; the per-step RCCL all-gather of the action gradients is
 the only exchange); the timed region is bracketed by barriers and the max
 over ranks is used.  The ranks come from torchrun (WORLD_SIZE must equal
 --gpus) or, without a launcher, `bench.py --gpus N` spawns them itself.
+
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) sets up, warms up,
+times the N steps and prints the JSON line with the headline figure (and the
+per-launch kernel times its HIP events bracket inside the timed steps).
+`--dump-outputs DIR` also writes what the last timed step returned to its
+caller.  Everything that takes runs of its own -- the deterministic replay
+behind the contact / LCP statistics and the roofline, the second measurement
+on the STL-mesh Atlas, the CPU baseline -- is behind `--full`.
 """
 import argparse
 import json
@@ -172,11 +180,13 @@ def rank_inputs(world, sampler, batch, rank):
     return st, f, g
 
 
-def make_step(timestep, world, action, g, gather, dist, ws, status_acc=None, gathered=None):
+def make_step(timestep, world, action, g, gather, dist, ws, status_acc=None, gathered=None, last=None):
     """One bench step on this rank's shard: `timestep` forward over the
     batch, backward of the upstream gradient `g`, the per-world action
     gradients all-gathered over the process group when `gather` (appended to
-    `gathered` when given), the state advanced to the next state."""
+    `gathered` when given), the state advanced to the next state.  When
+    `last` (a dict) is given it holds, after every step, the tensors that step
+    handed its caller: the next state and the state / action gradients."""
 
     def one_step(state):
         s = state.detach().requires_grad_(True)
@@ -189,6 +199,8 @@ def make_step(timestep, world, action, g, gather, dist, ws, status_acc=None, gat
             out = gather_grads(dist, a.grad, ws)
             if gathered is not None:
                 gathered.append(out)
+        if last is not None:
+            last.update(next_state=nxt.detach(), grad_state=s.grad, grad_action=a.grad)
         return nxt.detach()
 
     return one_step
@@ -367,13 +379,35 @@ def cpu_baseline(make, batch, sampler, seconds_target=12.0):
                       f"(CPU restatement of the reference's step), {threads} threads, {dt:.1f}s"}
 
 
-def measure(wl, batch, steps, warmup, dist, rank, ws, dev, gather):
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(last, outdir, rank):
+    """--dump-outputs: the arrays the last timed step returned (next state,
+    state and action gradients of this rank's shard) as outdir/<name>.npy
+    (rank 0; <name>.rank<r>.npy for the other ranks), float64.  Should a
+    workload's outputs ever exceed 64 MB in all, each array keeps a fixed
+    seeded sample of its rows."""
+    os.makedirs(outdir, exist_ok=True)
+    arrays = {k: v.detach().cpu().numpy().astype(np.float64, copy=False) for k, v in last.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_LIMIT_BYTES:
+            keep = max(1, int(a.shape[0] * DUMP_LIMIT_BYTES / total))
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(outdir, name + ("" if rank == 0 else f".rank{rank}") + ".npy"), a)
+
+
+def measure(wl, batch, steps, warmup, dist, rank, ws, dev, gather, full=True, dump=None):
     """Time `steps` bench steps (after `warmup`) of workload `wl` on this
     rank's `batch` worlds; returns the measured numbers (value = worlds x
-    steps x ranks / max-over-ranks elapsed).  On a CPU device (the launcher's
-    gloo test, with a host timestep patched in by the test) only the timing
-    and the gather run: the kernel timers, status words, replay statistics and
-    roofline need the GPU."""
+    steps x ranks / max-over-ranks elapsed).  `dump`: directory that receives
+    the last timed step's outputs (dump_outputs).  `full` adds the replay
+    statistics and the roofline, which take a rollout of their own after the
+    timed region.  On a CPU device (the launcher's gloo test, with a host
+    timestep patched in by the test) only the timing and the gather run: the
+    kernel timers, status words, replay statistics and roofline need the
+    GPU."""
     wl_name, make, sampler, metric, default_batch = WORKLOADS[wl]
     batch = batch if batch > 0 else default_batch
     gpu = dev.type == "cuda"
@@ -393,7 +427,8 @@ def measure(wl, batch, steps, warmup, dist, rank, ws, dev, gather):
         world.setStatusPolicy("record")
         timer.wrap(world.native())
         status_acc = torch.zeros(batch, dtype=torch.int32, device=dev)
-    one_step = make_step(nimble.timestep, world, action, g, gather, dist, ws, status_acc)
+    last = {} if dump else None
+    one_step = make_step(nimble.timestep, world, action, g, gather, dist, ws, status_acc, last=last)
     for _ in range(warmup):
         state = one_step(state)
     timer.enabled = gpu
@@ -402,15 +437,20 @@ def measure(wl, batch, steps, warmup, dist, rank, ws, dev, gather):
     out = {"wl": wl, "wl_name": wl_name, "metric": metric, "make": make, "sampler": sampler, "batch": batch, "n": n,
            "value": batch * ws * steps / elapsed, "ms_per_step": elapsed / steps * 1e3, "cstats": None,
            "flops": None}
+    if last:
+        dump_outputs(last, dump, rank)
     if not gpu:
         return out
     bad = int(((status_acc & _native.ST_DIVERGES) != 0).sum().item())
     if bad:
         raise SystemExit(f"bench ({wl}): {bad} world(s) left the reference's physics "
                          f"({_native.status_message(int(np.bitwise_or.reduce(status_acc.cpu().numpy())))})")
-    cstats = rollout_stats(world, state0, action, warmup, steps)
     fwd_ms = timer.mean_ms(timer.fwd)
     bwd_ms = timer.mean_ms(timer.bwd)
+    out.update(fwd_ms=fwd_ms, bwd_ms=bwd_ms)
+    if not full:
+        return out
+    cstats = rollout_stats(world, state0, action, warmup, steps)
     flops = _native.flop_estimate(world, cstats["rows"], cstats["clamping"])
     dom = "backward" if bwd_ms >= fwd_ms else "forward"
     dom_ms = max(bwd_ms, fwd_ms)
@@ -419,7 +459,7 @@ def measure(wl, batch, steps, warmup, dist, rank, ws, dev, gather):
     one_row = "nimble_forward_mesh_kernel" if (dom == "forward" and wl == "atlas_mesh") else f"nimble_{dom}_kernel"
     traffic, traffic_src = pmc_traffic(wl, [one_row] + ([f"nimble_{dom}_wide_kernel"] if wl == "atlas_mesh" else []),
                                        batch)
-    out.update(cstats=cstats, fwd_ms=fwd_ms, bwd_ms=bwd_ms, dom=dom, achieved=achieved, flops=flops,
+    out.update(cstats=cstats, dom=dom, achieved=achieved, flops=flops,
                traffic=traffic, traffic_src=traffic_src)
     sc = cstats.get("solver_counts")
     if sc is not None:
@@ -498,12 +538,13 @@ def report(args, r, mesh, ws, gather):
                          "contacts_per_world": cstats["contacts"], "lcp_rows_per_world": cstats["rows"],
                          "clamping_rows_per_world": cstats["clamping"],
                          "worlds_in_contact": cstats["worlds_in_contact"], "contact_stats_source": cstats["source"]}
-    if r["flops"] is not None:
+    if r.get("fwd_ms") is not None:
         out["kernels_ms"] = {"forward": r["fwd_ms"], "backward": r["bwd_ms"]}
+    if r["flops"] is not None:
         out["roofline"] = roofline(r, args.workload)
     if mesh is not None:
         out["atlas_mesh"] = mesh_report(args, mesh)
-    if not args.no_cpu_baseline and args.device == "cuda":
+    if args.full and not args.no_cpu_baseline and args.device == "cuda":
         out["cpu_baseline"] = cpu_baseline(r["make"], 16, r["sampler"])
     return out
 
@@ -515,9 +556,16 @@ def parse_args(argv=None):
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=0, help="worlds per GPU (default: the workload's)")
     ap.add_argument("--workload", default="atlas", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline's timed steps also run what takes runs of its own: the replay "
+                         "behind the contact / LCP statistics and the roofline, the second measurement on the "
+                         "STL-mesh Atlas, the CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step returned (next state, state and action gradients) "
+                         "as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-mesh", action="store_true",
-                    help="skip the second measurement of the reference atlas_bench's STL-mesh Atlas")
+                    help="with --full: skip the second measurement of the reference atlas_bench's STL-mesh Atlas")
     ap.add_argument("--gather-grads", type=int, default=-1,
                     help="all-gather action gradients each step (default: on when N > 1)")
     ap.add_argument("--device", default="cuda", choices=("cuda", "cpu"),
@@ -538,12 +586,13 @@ def run(args):
     else:
         dev = torch.device("cpu")
     gather = (ws > 1) if args.gather_grads < 0 else bool(args.gather_grads)
-    r = measure(args.workload, args.batch, args.steps, args.warmup, dist, rank, ws, dev, gather)
+    r = measure(args.workload, args.batch, args.steps, args.warmup, dist, rank, ws, dev, gather, full=args.full,
+                dump=args.dump_outputs)
     # the reference atlas_bench's own model (atlas_v3_no_head.urdf, 29 STL
     # colliders), measured after the headline's timed region on the same
     # ranks: reported beside the headline, never as `value`
     mesh = None
-    if args.workload == "atlas" and not args.no_mesh:
+    if args.full and args.workload == "atlas" and not args.no_mesh:
         mesh = measure("atlas_mesh", args.batch, min(args.steps, 20), min(args.warmup, 3), dist, rank, ws, dev, gather)
     if rank == 0:
         out = report(args, r, mesh, ws, gather)

@@ -19,7 +19,7 @@ closed forms derived by hand, not against its own identities:
   Euler) rollout staying within its O(dt) band;
 * the URDF loader's masses, COMs, inertias and joint frames of the bench Atlas
   (data/sdf/atlas/atlas_v3_box_colliders.urdf) against the URDF text, parsed
-  here independently (skipped where the reference is absent).
+  here independently (the URDF is stored under tests/golden/reference_models).
 """
 import json
 import math
@@ -34,7 +34,8 @@ from nimblephysics_amd import dynamics as D
 import nimblephysics_amd as nimble
 from oracle import oracle as O
 
-REF_ATLAS = "/root/reference/data/sdf/atlas/atlas_v3_box_colliders.urdf"
+REF_ATLAS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_models", "data", "sdf",
+                         "atlas", "atlas_v3_box_colliders.urdf")
 G = 9.81
 
 
@@ -174,7 +175,6 @@ def _nums(s, default="0 0 0"):
     return np.array([float(t) for t in (s or default).split()])
 
 
-@pytest.mark.skipif(not os.path.exists(REF_ATLAS), reason="reference data not present")
 def test_atlas_asset_matches_urdf_text():
     """Masses, COMs, inertia tensors, joint origins and axes of the bench
     Atlas asset (what the GPU box loads) against the URDF's own numbers."""

@@ -11,8 +11,9 @@ positions.
   colliders with scale, a "world" root; a .skel world with a skeleton frame,
   eulerXYZ transforms, init_pos, joint dynamics and limits, joints listed
   child-before-parent (getNextJointAndNodePair order);
-* the reference's own model files when /root/reference is present (this
-  container only): Atlas with box and with STL mesh colliders, the cartpole
+* the reference's own model files, stored under tests/golden/reference_models
+  (the URDF / .skel texts and the STL meshes they name, in the reference's
+  data/ layout): Atlas with box and with STL mesh colliders, the cartpole
   URDF, the ground and half_cheetah.skel.
 
 The C++ API scans every mesh vertex (no hull-candidate mask), so that one
@@ -32,7 +33,7 @@ from nimblephysics_amd import urdf as _urdf
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EXE = os.path.join(ROOT, "tests", "cpp", "world_api_test")
-REF = "/root/reference"
+REF = os.path.join(ROOT, "tests", "golden", "reference_models")
 
 
 def _cpp(mode, path):
@@ -204,7 +205,6 @@ REF_URDFS = ["data/sdf/atlas/atlas_v3_box_colliders.urdf", "data/sdf/atlas/atlas
              "data/sdf/atlas/ground.urdf", "data/urdf/cartpole.urdf"]
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference model files are only in the build container")
 @pytest.mark.parametrize("rel", REF_URDFS)
 def test_reference_urdf(rel):
     path = os.path.join(REF, rel)
@@ -213,7 +213,6 @@ def test_reference_urdf(rel):
     _compare(_cpp("describe-urdf", path), w)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference model files are only in the build container")
 def test_reference_skel():
     path = os.path.join(REF, "data/skel/half_cheetah.skel")
     _compare(_cpp("describe-skel", path), _skel.read_world(path))
