@@ -93,7 +93,8 @@ static Layout makeLayout(const ModelDev& m, bool backward, int poolRows) {
   if (backward) {
     // adjoint vectors (alpha..kappa per body); afterwards the workspace of
     // the contact-geometry terms, the M-derivative field pairs and the free
-    // joint finite differences
+    // joint finite differences.  (Wt directly behind adj: two M-derivative
+    // pairs per pass use both, 48 nb doubles, as one block.)
     L.adj = take(42 * nb > 24 * 6 ? 42 * nb : 24 * 6); L.Wt = take(6 * nb);
     L.scratch = L.adj;
     L.w = take(n); L.gp = take(n); L.gv = take(n);
@@ -246,6 +247,10 @@ int nimble_world_create(const nimble_world_desc* d, nimble_world_t* out) {
   if (const char* e = getenv("NIMBLE_AMD_POST_SPLIT")) m.postSplit = atoi(e) != 0;
   m.pinvMfma = 1;
   if (const char* e = getenv("NIMBLE_AMD_PINV_MFMA")) m.pinvMfma = atoi(e) != 0 ? 1 : 0;
+  m.bwdMFuse = 1;
+  if (const char* e = getenv("NIMBLE_AMD_BWD_MFUSE")) m.bwdMFuse = atoi(e) != 0 ? 1 : 0;
+  m.bwdSolve2 = 1;
+  if (const char* e = getenv("NIMBLE_AMD_BWD_SOLVE2")) m.bwdSolve2 = atoi(e) != 0 ? 1 : 0;
   // NIMBLE_AMD_GUARD_TEST="sites:stride:offset" (tests only): force the
   // deadlock guard to expire at the wait sites `sites` (contact.cuh GW_*
   // mask) in the worlds with index % stride == offset

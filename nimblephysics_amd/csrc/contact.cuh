@@ -3260,7 +3260,9 @@ __device__ int contactBackwardPrep(const ModelDev& md, double* s, const Layout& 
       }
       X[1] = a1; X[2] = a2; X[3] = a3; X[4] = a4;
     }
+    STAMP(32);
     cholSolveReg<5>(Lm, dinv, X, n, lane);
+    STAMP(33);
     if (lane < n) {
       double* nv = P.NV + lane * NV_COLS;
       const double d = X[1] / dt;
@@ -3321,6 +3323,7 @@ __device__ int contactBackwardPrep(const ModelDev& md, double* s, const Layout& 
       X[0] = a0; X[1] = a1; X[2] = a2; X[3] = a3;
       mu = a0;
     }
+    STAMP(36);
     cholSolveReg<4>(Lm, dinv, X, n, lane);
     if (lane < n) {
       double* nv = P.NV + lane * NV_COLS;
@@ -4083,13 +4086,118 @@ __device__ double contactGTermsAll(const ModelDev& md, double* s, const Layout& 
 // subtree momentum sum_{b in sub(k)} I_b V_x,b.  For each of the four (a, c)
 // column pairs of NV, lane b builds both fields' twists and momenta I_b V
 // (world inertias are formed once, kept as their 3x3 rotational block, world
-// COM and mass: 13 doubles per body after the 2 x nb x 12 field doubles in
-// `buf`), then the momenta are summed over each subtree level by level.
-__device__ double mFieldsTerm(const ModelDev& md, double* s, const Layout& L, const double* NV, double* buf, int lane,
-                              int k, const double* Z, double coefDelta, double imp) {
+// COM and mass: 13 doubles per body in `wI`), then the momenta are summed over
+// each subtree along the edge list.
+//
+// The pairs are independent, so a pass takes NP of them (2 NP fields of
+// nb x 12 doubles in `buf`): the dof loop shares its S_r loads among the
+// fields, one walk of the edge list sums all fields' momenta (lane = field x
+// component) and one pair of barriers serves them all.  Every element keeps
+// the operation order of the one-pair pass and `total` takes the pairs in
+// ascending order, so NP = 1 and NP = 2 give the same bits.
+template <int NP>
+__device__ __forceinline__ double mFieldPasses(const ModelDev& md, const double* s, const Layout& L, const double* NV,
+                                               int ldNV, double* buf, const double* wI, int lane, int k, const double* Z,
+                                               const double (&coef)[4], int npairs
+#ifdef NIMBLE_STAGE_TIMING
+                                               , double* g_stamp
+#endif
+) {
+  constexpr int NF = 2 * NP;  // fields of a pass: NV columns 2 p0 .. 2 p0 + NF - 1
+  const int nb = md.nb;
+  double total = 0.0;
+  for (int p0 = 0; p0 < npairs; p0 += NP) {
+    TACC_BEGIN(tV);
+    if (lane < nb) {
+      const int b = lane;
+      double V[NF][6];
+      for (int f = 0; f < NF; f++)
+        for (int i = 0; i < 6; i++) V[f][i] = 0.0;
+      const unsigned long long an = md.anc[b];
+      const double* g = NV + 2 * p0;
+#pragma unroll 4
+      for (int r = 0; r < md.n; r++) {
+        const bool in = (an >> md.dofBody[r]) & 1ull;
+        double xf[NF];
+        for (int f = 0; f < NF; f++) xf[f] = in ? g[r * ldNV + f] : 0.0;
+        const double* S = s + L.Sw + 6 * r;
+        for (int i = 0; i < 6; i++)
+          for (int f = 0; f < NF; f++) V[f][i] = fma(S[i], xf[f], V[f][i]);
+      }
+      const double* w = wI + 13 * b;
+      const double m = w[12];
+      const double C[9] = {0, -w[11], w[10], w[11], 0, -w[9], -w[10], w[9], 0};
+      double I[36];
+      for (int r = 0; r < 3; r++)
+        for (int c = 0; c < 3; c++) {
+          I[r * 6 + c] = w[r * 3 + c];
+          I[r * 6 + c + 3] = m * C[r * 3 + c];
+          I[(r + 3) * 6 + c] = m * C[c * 3 + r];
+          I[(r + 3) * 6 + c + 3] = (r == c) ? m : 0.0;
+        }
+      for (int f = 0; f < NF; f++) {
+        double* F = buf + (f * nb + b) * 12;
+        double h[6];
+        mv6(I, V[f], h);
+        for (int i = 0; i < 6; i++) { F[i] = V[f][i]; F[6 + i] = h[i]; }
+      }
+    }
+    WSYNC();
+    TACC_END(52, tV);
+    TACC_BEGIN(tW);
+    // subtree momenta in place over the deepest-child-first edge list (lane =
+    // field x component; see composites) -- instead of every lane reading all
+    // nb bodies' 12 momenta (the four worlds of a CU share the LDS bandwidth)
+    if (lane < 6 * NF) {
+      double* base = buf + (lane / 6) * nb * 12 + 6 + (lane % 6);
+#pragma unroll 4
+      for (int e = 0; e < md.numAcc; e++) {
+        const int p = md.accEdge[e][0], c = md.accEdge[e][1];
+        base[p * 12] += base[c * 12];
+      }
+    }
+    WSYNC();
+    TACC_END(53, tW);
+    TACC_BEGIN(tR);
+    // dof k reads its body's subtree momenta
+    const int bk = k < md.n ? md.dofBody[k] : 0;
+    for (int q = 0; q < NP; q++) {
+      const double* Fa = buf + 2 * q * nb * 12;
+      const double* Fc = buf + (2 * q + 1) * nb * 12;
+      double ha[6], hc[6];
+      for (int i = 0; i < 6; i++) { ha[i] = Fa[bk * 12 + 6 + i]; hc[i] = Fc[bk * 12 + 6 + i]; }
+      if (k < md.n) {
+        const int lam = md.parent[bk];
+        double val = 0.0;
+        if (lam >= 0) {
+          double t[6];
+          crm(Z, Fc + lam * 12, t);
+          val -= dot6(t, ha);
+          crm(Z, Fa + lam * 12, t);
+          val -= dot6(t, hc);
+        }
+        total += coef[p0 + q] * val;
+      }
+    }
+    WSYNC();
+    TACC_END(59, tR);
+#ifdef NIMBLE_STAGE_TIMING
+    if (lane == 0 && g_stamp) g_stamp[89] += 1.0;  // (passes: a count)
+#endif
+  }
+  return total;
+}
+
+// `buf` holds 24 nb doubles and `wI` 13 nb; with `fuse` (two pairs per pass)
+// `buf` holds 48 nb.  NV: the pairs' columns 0..7, leading dimension ldNV.
+__device__ double mFieldsTerm(const ModelDev& md, double* s, const Layout& L, const double* NV, int ldNV, double* buf,
+                              double* wI, bool fuse, int lane, int k, const double* Z, double coefDelta, double imp
+#ifdef NIMBLE_STAGE_TIMING
+                              , double* g_stamp
+#endif
+) {
   const int nb = md.nb;
   const double coef[4] = {coefDelta, 1.0, -imp, -imp};
-  double* wI = buf + 24 * nb;
   if (lane < nb) {
     // worldInertia's arithmetic, stored compactly
     const int b = lane;
@@ -4114,75 +4222,14 @@ __device__ double mFieldsTerm(const ModelDev& md, double* s, const Layout& L, co
     w[9] = cw[0]; w[10] = cw[1]; w[11] = cw[2]; w[12] = m;
   }
   WSYNC();
-  double total = 0.0;
   // the pseudo-inverse branch's two pairs carry the factor -imp: skipped
   // when Q has full rank
   const int npairs = imp != 0.0 ? 4 : 2;
-  for (int pr = 0; pr < npairs; pr++) {
-    if (lane < nb) {
-      const int b = lane;
-      double Va[6] = {0, 0, 0, 0, 0, 0}, Vc[6] = {0, 0, 0, 0, 0, 0};
-      const unsigned long long an = md.anc[b];
-      const double* ga = NV + 2 * pr;
-      const double* gc = NV + 2 * pr + 1;
-#pragma unroll 4
-      for (int r = 0; r < md.n; r++) {
-        const bool in = (an >> md.dofBody[r]) & 1ull;
-        const double xa = in ? ga[r * NV_COLS] : 0.0, xc = in ? gc[r * NV_COLS] : 0.0;
-        const double* S = s + L.Sw + 6 * r;
-        for (int i = 0; i < 6; i++) {
-          Va[i] = fma(S[i], xa, Va[i]);
-          Vc[i] = fma(S[i], xc, Vc[i]);
-        }
-      }
-      const double* w = wI + 13 * b;
-      const double m = w[12];
-      const double C[9] = {0, -w[11], w[10], w[11], 0, -w[9], -w[10], w[9], 0};
-      double I[36];
-      for (int r = 0; r < 3; r++)
-        for (int c = 0; c < 3; c++) {
-          I[r * 6 + c] = w[r * 3 + c];
-          I[r * 6 + c + 3] = m * C[r * 3 + c];
-          I[(r + 3) * 6 + c] = m * C[c * 3 + r];
-          I[(r + 3) * 6 + c + 3] = (r == c) ? m : 0.0;
-        }
-      double* Fa = buf + b * 12;
-      double* Fc = buf + (nb + b) * 12;
-      double ha[6], hc[6];
-      mv6(I, Va, ha);
-      mv6(I, Vc, hc);
-      for (int i = 0; i < 6; i++) { Fa[i] = Va[i]; Fa[6 + i] = ha[i]; Fc[i] = Vc[i]; Fc[6 + i] = hc[i]; }
-    }
-    WSYNC();
-    // subtree momenta in place over the deepest-child-first edge list (lane =
-    // field x component; see composites) -- instead of every lane reading all
-    // nb bodies' 12 momenta (the four worlds of a CU share the LDS bandwidth)
-    if (lane < 12) {
-      double* base = buf + (lane < 6 ? 0 : nb * 12) + 6 + (lane % 6);
-#pragma unroll 4
-      for (int k = 0; k < md.numAcc; k++) {
-        const int p = md.accEdge[k][0], c = md.accEdge[k][1];
-        base[p * 12] += base[c * 12];
-      }
-    }
-    WSYNC();
-    // dof k reads its body's subtree momenta
-    const int bk = k < md.n ? md.dofBody[k] : 0;
-    double ha[6], hc[6];
-    for (int i = 0; i < 6; i++) { ha[i] = buf[bk * 12 + 6 + i]; hc[i] = buf[(nb + bk) * 12 + 6 + i]; }
-    if (k < md.n) {
-      const int lam = md.parent[bk];
-      double val = 0.0;
-      if (lam >= 0) {
-        double t[6];
-        crm(Z, buf + (nb + lam) * 12, t);
-        val -= dot6(t, ha);
-        crm(Z, buf + lam * 12, t);
-        val -= dot6(t, hc);
-      }
-      total += coef[pr] * val;
-    }
-    WSYNC();
-  }
-  return total;
+#ifdef NIMBLE_STAGE_TIMING
+  if (fuse) return mFieldPasses<2>(md, s, L, NV, ldNV, buf, wI, lane, k, Z, coef, npairs, g_stamp);
+  return mFieldPasses<1>(md, s, L, NV, ldNV, buf, wI, lane, k, Z, coef, npairs, g_stamp);
+#else
+  if (fuse) return mFieldPasses<2>(md, s, L, NV, ldNV, buf, wI, lane, k, Z, coef, npairs);
+  return mFieldPasses<1>(md, s, L, NV, ldNV, buf, wI, lane, k, Z, coef, npairs);
+#endif
 }

@@ -94,6 +94,14 @@ struct ModelDev {
   // (contact.cuh pinvColumnsMfma) when the factor has full rank; 0: the
   // per-column solves (NIMBLE_AMD_PINV_MFMA=0, measurements)
   int pinvMfma;
+  // the backward's M-derivative field pairs two per pass (contact.cuh
+  // mFieldsTerm) where the world inertias find a place on chip beside the
+  // four fields (timestep.hip backwardItems); 0: one pair per pass
+  // (NIMBLE_AMD_BWD_MFUSE=0, tests and measurements)
+  int bwdMFuse;
+  // the contact-free backward's two Minv products as one batched solve; 0:
+  // one after the other (NIMBLE_AMD_BWD_SOLVE2=0, tests and measurements)
+  int bwdSolve2;
   // the deadlock guard's test switch (contact.cuh GW_*): the waits at the
   // sites in guardSites expire at once in the worlds env with env %
   // guardStride == guardOffset (NIMBLE_AMD_GUARD_TEST="sites:stride:offset",

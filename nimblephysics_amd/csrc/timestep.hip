@@ -800,8 +800,18 @@ __device__ __forceinline__ void backwardItems(const ModelDev* __restrict__ mdp, 
         w[i] = s[L.gv + i];
       }
       WSYNC();
-      cholSolve(s + L.M, s + L.dinv, x, n, lane);  // x = y = Minv z  => a* = y / dt
-      cholSolve(s + L.M, s + L.dinv, w, n, lane);  // w = Minv gv
+      if (md.bwdSolve2) {
+        // x = y = Minv z  => a* = y / dt, and w = Minv gv: two independent
+        // chains in one batched substitution, each with its own operations
+        double xw[2] = {lane < n ? x[lane] : 0.0, lane < n ? w[lane] : 0.0};
+        cholSolveReg<2>(s + L.M, s + L.dinv, xw, n, lane);
+        WSYNC();
+        if (lane < n) { x[lane] = xw[0]; w[lane] = xw[1]; }
+        WSYNC();
+      } else {
+        cholSolve(s + L.M, s + L.dinv, x, n, lane);
+        cholSolve(s + L.M, s + L.dinv, w, n, lane);
+      }
       for (int i = lane; i < n; i += WAVE) x[i] /= dt;
       WSYNC();
     }
@@ -886,7 +896,42 @@ __device__ __forceinline__ void backwardItems(const ModelDev* __restrict__ mdp, 
       WSYNC();
       TACC_END(80, tG);
       TACC_BEGIN(tM);
-      const double mterm = mFieldsTerm(md, s, L, P.NV, buf, lane, k, Z, -dt, (double)imp);
+      // two pairs per pass take the adjoint area and Wt behind it (42nb + 6nb,
+      // both dead) for their four fields; the 13nb world inertias then need a
+      // place of their own on chip: the Cholesky factor's (only the solves of
+      // the contact prep read it, and every item loads it anew), else the
+      // pool's gRows / TAB slots, which the G terms have finished with, or,
+      // for a world whose pool is in the HBM workspace, the idle LDS pool
+      // area.  Such a world also gets a copy of NV's eight field columns
+      // there, which every lane reads once per dof.  Otherwise one pair per
+      // pass, inertias behind the fields.
+      bool mfuse = false;
+      double* wI = buf + 24 * md.nb;
+      const double* NVf = P.NV;
+      int ldNV = NV_COLS;
+      if (md.bwdMFuse) {
+        const int wId = (13 * md.nb + 1) & ~1;
+        const bool onChip = bwdPoolDoubles(m, n) <= L.poolCap;
+        int idle = onChip ? 0 : L.poolCap;  // doubles free at s + L.pool
+        double* free = s + L.pool;
+        if (n * (n + 1) / 2 >= wId) { mfuse = true; wI = s + L.M; }
+        else if (onChip && (n + 12) * m >= wId) { mfuse = true; wI = P.gRows; }
+        else if (idle >= wId) { mfuse = true; wI = free; free += wId; idle -= wId; }
+        if (mfuse) {
+          if (idle >= 8 * n) {
+            double* stage = free;
+            if (lane < n)
+              for (int c = 0; c < 8; c++) stage[lane * 8 + c] = P.NV[lane * NV_COLS + c];
+            NVf = stage;  // (mFieldsTerm's first barrier orders the copy)
+            ldNV = 8;
+          }
+        }
+      }
+#ifdef NIMBLE_STAGE_TIMING
+      const double mterm = mFieldsTerm(md, s, L, NVf, ldNV, buf, wI, mfuse, lane, k, Z, -dt, (double)imp, g_stamp);
+#else
+      const double mterm = mFieldsTerm(md, s, L, NVf, ldNV, buf, wI, mfuse, lane, k, Z, -dt, (double)imp);
+#endif
       TACC_END(81, tM);
       if (k < n) {
         gq += gterm;
