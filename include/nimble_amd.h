@@ -246,7 +246,8 @@ int nimble_backward_masses(nimble_world_t world, int32_t batch, const double* st
  *   grad_inertia [batch][num_bodies][10]  device
  * The Python / C++ layers pick the tuned entries' components (INERTIA_MASS,
  * INERTIA_COM, INERTIA_COM_MU (beta-weighted COM), INERTIA_DIAGONAL,
- * INERTIA_OFF_DIAGONAL, INERTIA_FULL).
+ * INERTIA_OFF_DIAGONAL, INERTIA_FULL).  The per-world parameter array
+ * body_inertia of the `_pw` entry points below has this layout and order.
  */
 int nimble_backward_inertia(nimble_world_t world, int32_t batch, const double* state,
                             const double* forces, double* snapshot,
@@ -289,6 +290,53 @@ int nimble_constraint_force_jacobians(nimble_world_t world, int32_t batch, const
                                       const double* forces, const double* snapshot,
                                       double* dfc_dstate, double* dfc_dforces,
                                       double* workspace, void* stream);
+
+/*
+ * Per-world body inertial parameters.  Each `_pw` entry point is its sibling
+ * above with one more argument:
+ *   body_inertia [batch][num_bodies][10]  device, read only
+ * ten doubles per body of every world, bodies in the order of
+ * nimble_world_desc (num_bodies of them: the massless frames of compound-joint
+ * chains included), components in WithRespectToMass's INERTIA_FULL order
+ * (dart/neural/WithRespectToMass.cpp:35-181): mass, local COM x y z, moment
+ * about the COM Ixx Iyy Izz Ixy Ixz Iyz -- the layout of grad_inertia, so
+ * nimble_backward_inertia_pw's output is the gradient with respect to this
+ * array, element by element.  World b's step and its derivatives then use
+ * row b wherever the siblings use the description's mass / com / moment; the
+ * arithmetic is the siblings', so a row holding the description's values
+ * gives the siblings' bits.  Friction, restitution, damping and geometry stay
+ * the model's.  NULL selects the model's own parameters: the existing entry
+ * points are these with NULL.  The array is not validated on the device (a
+ * non-positive mass or an indefinite moment gives what the arithmetic gives).
+ * A forward and every backward / Jacobian call on its snapshot must be given
+ * the same array.
+ */
+int nimble_forward_pw(nimble_world_t world, int32_t batch, const double* state,
+                      const double* forces, double* lcp_cache, double* next_state,
+                      double* snapshot, const double* body_inertia, void* stream);
+int nimble_backward_pw(nimble_world_t world, int32_t batch, const double* state,
+                       const double* forces, double* snapshot,
+                       const double* grad_next_state, double* grad_state,
+                       double* grad_forces, const double* body_inertia, void* stream);
+int nimble_backward_masses_pw(nimble_world_t world, int32_t batch, const double* state,
+                              const double* forces, double* snapshot,
+                              const double* grad_next_state, double* grad_state,
+                              double* grad_forces, double* grad_masses,
+                              const double* body_inertia, void* stream);
+int nimble_backward_inertia_pw(nimble_world_t world, int32_t batch, const double* state,
+                               const double* forces, double* snapshot,
+                               const double* grad_next_state, double* grad_state,
+                               double* grad_forces, double* grad_inertia,
+                               const double* body_inertia, void* stream);
+int nimble_jacobians_pw(nimble_world_t world, int32_t batch, const double* state,
+                        const double* forces, const double* snapshot,
+                        double* state_jacobian, double* force_jacobian,
+                        double* workspace, const double* body_inertia, void* stream);
+int nimble_constraint_force_jacobians_pw(nimble_world_t world, int32_t batch, const double* state,
+                                         const double* forces, const double* snapshot,
+                                         double* dfc_dstate, double* dfc_dforces,
+                                         double* workspace, const double* body_inertia,
+                                         void* stream);
 
 /* Last error message (thread-local). */
 const char* nimble_last_error(void);

@@ -50,6 +50,14 @@ def lib():
         L.nimble_constraint_force_jacobians.restype = C.c_int
         L.nimble_jacobians.restype = C.c_int
         L.nimble_num_collision_pairs.argtypes = [C.c_void_p]
+        # the siblings with per-world body inertial parameters: body_inertia
+        # ahead of the stream
+        for name, buffers in (("nimble_forward_pw", 6), ("nimble_backward_pw", 7), ("nimble_backward_masses_pw", 8),
+                              ("nimble_backward_inertia_pw", 8), ("nimble_jacobians_pw", 7),
+                              ("nimble_constraint_force_jacobians_pw", 7)):
+            f = getattr(L, name)
+            f.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * buffers + [C.c_void_p]
+            f.restype = C.c_int
         L.nimble_num_collision_pairs.restype = C.c_int32
         _lib = L
     return _lib
@@ -176,6 +184,21 @@ class DeviceWorld:
             if t is not None and not t.is_contiguous():
                 raise ValueError("nimblephysics_amd buffers must be contiguous")
 
+    def _inertia(self, B, body_inertia):
+        """Checks the optional per-world parameter array (include/nimble_amd.h
+        body_inertia: [B, num_bodies, 10] float64, INERTIA_FULL order per
+        body) before anything else is looked at; None selects the model's
+        own parameters."""
+        t = body_inertia
+        if t is None:
+            return
+        if tuple(t.shape) != (B, self.nb, 10):
+            raise ValueError(f"body_inertia shape {tuple(t.shape)} != ({B}, {self.nb}, 10)")
+        if str(t.dtype) != "torch.float64":
+            raise TypeError("body_inertia must be float64 (the reference's s_t); got " + str(t.dtype))
+        if not t.is_contiguous():
+            raise ValueError("nimblephysics_amd buffers must be contiguous")
+
     def status(self, snapshot):
         """Status bits per world ([B] int32, device) of the forward that wrote
         `snapshot`; zeros for models without collision pairs."""
@@ -184,87 +207,126 @@ class DeviceWorld:
             return torch.zeros(snapshot.shape[0], dtype=torch.int32, device=snapshot.device)
         return snapshot[:, SN_STATUS].to(torch.int32)
 
-    def forward(self, state, forces, lcp_cache, next_state, snapshot, stream_ptr: int):
-        _require_device(state, forces, lcp_cache, next_state, snapshot)
+    def forward(self, state, forces, lcp_cache, next_state, snapshot, stream_ptr: int, body_inertia=None):
+        """nimble_forward; with `body_inertia` [B, num_bodies, 10] every world
+        steps with its own body parameters (nimble_forward_pw), and the
+        backward / Jacobian calls on its snapshot take the same tensor."""
         B = state.shape[0]
-        self._on_my_device(state, forces, lcp_cache, next_state, snapshot)
+        self._inertia(B, body_inertia)
+        _require_device(state, forces, lcp_cache, next_state, snapshot, body_inertia)
+        self._on_my_device(state, forces, lcp_cache, next_state, snapshot, body_inertia)
         self._shapes(B, state, forces, snapshot, lcp_cache)
+        if body_inertia is not None:
+            _check(lib().nimble_forward_pw(self.h, B, _ptr(state), _ptr(forces), _ptr(lcp_cache), _ptr(next_state),
+                                           _ptr(snapshot), _ptr(body_inertia), C.c_void_p(stream_ptr)))
+            return
         _check(lib().nimble_forward(self.h, B, _ptr(state), _ptr(forces), _ptr(lcp_cache), _ptr(next_state),
                                     _ptr(snapshot), C.c_void_p(stream_ptr)))
 
-    def backward(self, state, forces, snapshot, grad_next, grad_state, grad_forces, stream_ptr: int):
-        _require_device(state, forces, snapshot, grad_next, grad_state, grad_forces)
+    def backward(self, state, forces, snapshot, grad_next, grad_state, grad_forces, stream_ptr: int,
+                 body_inertia=None):
         B = state.shape[0]
-        self._on_my_device(state, forces, snapshot, grad_next, grad_state, grad_forces)
+        self._inertia(B, body_inertia)
+        _require_device(state, forces, snapshot, grad_next, grad_state, grad_forces, body_inertia)
+        self._on_my_device(state, forces, snapshot, grad_next, grad_state, grad_forces, body_inertia)
         self._shapes(B, state, forces, snapshot)
         self._shapes(B, grad_next, grad_forces)
         self._shapes(B, grad_state)
+        if body_inertia is not None:
+            _check(lib().nimble_backward_pw(self.h, B, _ptr(state), _ptr(forces), _ptr(snapshot), _ptr(grad_next),
+                                            _ptr(grad_state), _ptr(grad_forces), _ptr(body_inertia),
+                                            C.c_void_p(stream_ptr)))
+            return
         _check(lib().nimble_backward(self.h, B, _ptr(state), _ptr(forces), _ptr(snapshot), _ptr(grad_next),
                                      _ptr(grad_state), _ptr(grad_forces), C.c_void_p(stream_ptr)))
 
     def backward_masses(self, state, forces, snapshot, grad_next, grad_state, grad_forces, grad_masses,
-                        stream_ptr: int):
+                        stream_ptr: int, body_inertia=None):
         """backward() plus dL/d(body masses) [B, num_bodies] (nimble_backward_masses)."""
-        _require_device(state, forces, snapshot, grad_next, grad_state, grad_forces, grad_masses)
         B = state.shape[0]
-        self._on_my_device(state, forces, snapshot, grad_next, grad_state, grad_forces, grad_masses)
+        self._inertia(B, body_inertia)
+        _require_device(state, forces, snapshot, grad_next, grad_state, grad_forces, grad_masses, body_inertia)
+        self._on_my_device(state, forces, snapshot, grad_next, grad_state, grad_forces, grad_masses, body_inertia)
         self._shapes(B, state, forces, snapshot)
         self._shapes(B, grad_next, grad_forces)
         self._shapes(B, grad_state)
         if tuple(grad_masses.shape) != (B, self.nb) or not grad_masses.is_contiguous():
             raise ValueError(f"grad_masses shape {tuple(grad_masses.shape)} != ({B}, {self.nb})")
+        if body_inertia is not None:
+            _check(lib().nimble_backward_masses_pw(self.h, B, _ptr(state), _ptr(forces), _ptr(snapshot),
+                                                   _ptr(grad_next), _ptr(grad_state), _ptr(grad_forces),
+                                                   _ptr(grad_masses), _ptr(body_inertia), C.c_void_p(stream_ptr)))
+            return
         _check(lib().nimble_backward_masses(self.h, B, _ptr(state), _ptr(forces), _ptr(snapshot), _ptr(grad_next),
                                             _ptr(grad_state), _ptr(grad_forces), _ptr(grad_masses),
                                             C.c_void_p(stream_ptr)))
 
     def backward_inertia(self, state, forces, snapshot, grad_next, grad_state, grad_forces, grad_inertia,
-                         stream_ptr: int):
+                         stream_ptr: int, body_inertia=None):
         """backward() plus dL/d(body inertia parameters) [B, num_bodies, 10] in
         INERTIA_FULL order (mass, COM xyz, Ixx Iyy Izz Ixy Ixz Iyz;
-        nimble_backward_inertia)."""
-        _require_device(state, forces, snapshot, grad_next, grad_state, grad_forces, grad_inertia)
+        nimble_backward_inertia): with `body_inertia`, the gradient with
+        respect to that array."""
         B = state.shape[0]
-        self._on_my_device(state, forces, snapshot, grad_next, grad_state, grad_forces, grad_inertia)
+        self._inertia(B, body_inertia)
+        _require_device(state, forces, snapshot, grad_next, grad_state, grad_forces, grad_inertia, body_inertia)
+        self._on_my_device(state, forces, snapshot, grad_next, grad_state, grad_forces, grad_inertia, body_inertia)
         self._shapes(B, state, forces, snapshot)
         self._shapes(B, grad_next, grad_forces)
         self._shapes(B, grad_state)
         if tuple(grad_inertia.shape) != (B, self.nb, 10) or not grad_inertia.is_contiguous():
             raise ValueError(f"grad_inertia shape {tuple(grad_inertia.shape)} != ({B}, {self.nb}, 10)")
+        if body_inertia is not None:
+            _check(lib().nimble_backward_inertia_pw(self.h, B, _ptr(state), _ptr(forces), _ptr(snapshot),
+                                                    _ptr(grad_next), _ptr(grad_state), _ptr(grad_forces),
+                                                    _ptr(grad_inertia), _ptr(body_inertia), C.c_void_p(stream_ptr)))
+            return
         _check(lib().nimble_backward_inertia(self.h, B, _ptr(state), _ptr(forces), _ptr(snapshot), _ptr(grad_next),
                                              _ptr(grad_state), _ptr(grad_forces), _ptr(grad_inertia),
                                              C.c_void_p(stream_ptr)))
 
-    def jacobians(self, state, forces, snapshot, stream_ptr: int):
+    def jacobians(self, state, forces, snapshot, stream_ptr: int, body_inertia=None):
         """(d next_state / d state [B, 2n, 2n], d next_state / d forces
         [B, 2n, n]) of the forward that wrote `snapshot` (nimble_jacobians)."""
         import torch
-        _require_device(state, forces, snapshot)
         B = state.shape[0]
-        self._on_my_device(state, forces, snapshot)
+        self._inertia(B, body_inertia)
+        _require_device(state, forces, snapshot, body_inertia)
+        self._on_my_device(state, forces, snapshot, body_inertia)
         self._shapes(B, state, forces, snapshot)
         n = self.n
         J = torch.empty((B, 2 * n, 2 * n), dtype=torch.float64, device=state.device)
         F = torch.empty((B, 2 * n, n), dtype=torch.float64, device=state.device)
         wsd = int(lib().nimble_jacobian_workspace_doubles(self.h, B))
         ws = torch.empty(wsd, dtype=torch.float64, device=state.device) if wsd > 0 else None
+        if body_inertia is not None:
+            _check(lib().nimble_jacobians_pw(self.h, B, _ptr(state), _ptr(forces), _ptr(snapshot), _ptr(J), _ptr(F),
+                                             _ptr(ws), _ptr(body_inertia), C.c_void_p(stream_ptr)))
+            return J, F
         _check(lib().nimble_jacobians(self.h, B, _ptr(state), _ptr(forces), _ptr(snapshot), _ptr(J), _ptr(F),
                                       _ptr(ws), C.c_void_p(stream_ptr)))
         return J, F
 
-    def constraint_force_jacobians(self, state, forces, snapshot, stream_ptr: int):
+    def constraint_force_jacobians(self, state, forces, snapshot, stream_ptr: int, body_inertia=None):
         """(d f_c / d state [B, MAX_LCP, 2n], d f_c / d forces [B, MAX_LCP, n])
         of the forward that wrote `snapshot` (nimble_constraint_force_jacobians;
         rows past each world's clamping count are zero)."""
         import torch
-        _require_device(state, forces, snapshot)
         B = state.shape[0]
-        self._on_my_device(state, forces, snapshot)
+        self._inertia(B, body_inertia)
+        _require_device(state, forces, snapshot, body_inertia)
+        self._on_my_device(state, forces, snapshot, body_inertia)
         self._shapes(B, state, forces, snapshot)
         n = self.n
         Js = torch.empty((B, MAX_LCP, 2 * n), dtype=torch.float64, device=state.device)
         Jf = torch.empty((B, MAX_LCP, n), dtype=torch.float64, device=state.device)
         wsd = int(lib().nimble_jacobian_workspace_doubles(self.h, B))
         ws = torch.empty(wsd, dtype=torch.float64, device=state.device) if wsd > 0 else None
+        if body_inertia is not None:
+            _check(lib().nimble_constraint_force_jacobians_pw(self.h, B, _ptr(state), _ptr(forces), _ptr(snapshot),
+                                                              _ptr(Js), _ptr(Jf), _ptr(ws), _ptr(body_inertia),
+                                                              C.c_void_p(stream_ptr)))
+            return Js, Jf
         _check(lib().nimble_constraint_force_jacobians(self.h, B, _ptr(state), _ptr(forces), _ptr(snapshot),
                                                        _ptr(Js), _ptr(Jf), _ptr(ws), C.c_void_p(stream_ptr)))
         return Js, Jf

@@ -61,6 +61,19 @@ extern "C" __global__ void nimble_backward_wide_kernel(const ModelDev*, int, con
                                                        double*, int, const double*, double*, double*, int, double*,
                                                        int, double*, int, int, int);
 
+// the instances that read per-world body inertial parameters (body_inertia
+// [batch][num_bodies][10], the last argument)
+extern "C" __global__ void nimble_forward_pw_kernel(const ModelDev*, Layout, const double*, const double*, double*,
+                                                    double*, double*, int, int, int, int, const double*);
+extern "C" __global__ void nimble_forward_mesh_pw_kernel(const ModelDev*, Layout, const double*, const double*,
+                                                         double*, double*, double*, int, int, int, int, const double*);
+extern "C" __global__ void nimble_backward_pw_kernel(const ModelDev*, int, const double*, const double*,
+                                                     double*, int, const double*, double*, double*, int, double*, int,
+                                                     double*, int, int, int, const double*);
+extern "C" __global__ void nimble_backward_wide_pw_kernel(const ModelDev*, int, const double*, const double*,
+                                                          double*, int, const double*, double*, double*, int, double*,
+                                                          int, double*, int, int, int, const double*);
+
 static void isoInverse(const double* T, double* O) {
   // [R|p]^-1 = [R^T | -R^T p]
   for (int r = 0; r < 3; r++)
@@ -481,6 +494,11 @@ static int gridFor(int batch) {
 
 int nimble_forward(nimble_world_t w, int32_t batch, const double* state, const double* forces, double* lcp_cache,
                    double* next_state, double* snapshot, void* stream) {
+  return nimble_forward_pw(w, batch, state, forces, lcp_cache, next_state, snapshot, nullptr, stream);
+}
+
+int nimble_forward_pw(nimble_world_t w, int32_t batch, const double* state, const double* forces, double* lcp_cache,
+                      double* next_state, double* snapshot, const double* body_inertia, void* stream) {
   if (!w || batch < 0) return fail(NIMBLE_ERR_INVALID, "bad arguments");
   if (batch == 0) return NIMBLE_OK;
   if (!state || !forces || !next_state || !snapshot || !lcp_cache) return fail(NIMBLE_ERR_INVALID, "null buffer");
@@ -507,7 +525,20 @@ int nimble_forward(nimble_world_t w, int32_t batch, const double* state, const d
       HIP_TRY(hipMemsetAsync(snapshot + (size_t)b0 * w->snapDoubles + SN_DEFERCNT, 0, DEFER_BUCKETS * sizeof(int), st));
     // (models with mesh colliders: the instance with the mesh-box narrow
     // phase inlined on the helper)
-    if (w->host.hasMesh)
+    // (per-world body parameters: the instances that read body_inertia; the
+    // wide kernel below reloads their dynamics cache and needs no inertia)
+    const double* bi = body_inertia ? body_inertia + (size_t)b0 * w->host.nb * 10 : nullptr;
+    if (bi && w->host.hasMesh)
+      hipLaunchKernelGGL(nimble_forward_mesh_pw_kernel, dim3(cnt), dim3(fwdThreads), lds, st, w->dev, w->fwd,
+                         state + b0 * 2 * n, forces + b0 * n, lcp_cache + (size_t)b0 * w->cacheDoubles,
+                         next_state + b0 * 2 * n, snapshot + (size_t)b0 * w->snapDoubles, w->snapDoubles,
+                         w->cacheDoubles, w->fwdDeferRows, wide && largestFirst ? 1 : 0, bi);
+    else if (bi)
+      hipLaunchKernelGGL(nimble_forward_pw_kernel, dim3(cnt), dim3(fwdThreads), lds, st, w->dev, w->fwd,
+                         state + b0 * 2 * n, forces + b0 * n, lcp_cache + (size_t)b0 * w->cacheDoubles,
+                         next_state + b0 * 2 * n, snapshot + (size_t)b0 * w->snapDoubles, w->snapDoubles,
+                         w->cacheDoubles, w->fwdDeferRows, wide && largestFirst ? 1 : 0, bi);
+    else if (w->host.hasMesh)
       hipLaunchKernelGGL(nimble_forward_mesh_kernel, dim3(cnt), dim3(fwdThreads), lds, st, w->dev, w->fwd,
                          state + b0 * 2 * n, forces + b0 * n, lcp_cache + (size_t)b0 * w->cacheDoubles,
                          next_state + b0 * 2 * n, snapshot + (size_t)b0 * w->snapDoubles, w->snapDoubles,
@@ -533,12 +564,24 @@ int nimble_forward(nimble_world_t w, int32_t batch, const double* state, const d
 }
 
 // the backward kernels: items of worlds with <= deferRows LCP rows, then (if
-// any world can have more) the two-rows-per-lane kernel for the others
+// any world can have more) the two-rows-per-lane kernel for the others.
+// bodyInertia != nullptr: the instances that read the worlds' own parameters.
 static hipError_t launchBackward(nimble_world_t w, int grid, hipStream_t st, int batch, const double* state,
                                  const double* forces, double* snapshot, const double* gradNext, double* gradState,
                                  double* gradForces, int rows, double* ws, int wsDoubles, double* gradMasses,
-                                 int fcMode, int massParams) {
+                                 int fcMode, int massParams, const double* bodyInertia) {
   const size_t lds = (size_t)w->bwd.total * sizeof(double);
+  if (bodyInertia) {
+    hipLaunchKernelGGL(nimble_backward_pw_kernel, dim3(grid), dim3(64), lds, st, w->dev, batch, state, forces,
+                       snapshot, w->snapDoubles, gradNext, gradState, gradForces, rows, ws, wsDoubles, gradMasses,
+                       fcMode, massParams, w->deferRows, bodyInertia);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess || w->host.numPairs == 0 || w->maxRows <= w->deferRows) return e;
+    hipLaunchKernelGGL(nimble_backward_wide_pw_kernel, dim3(grid), dim3(64), lds, st, w->dev, batch, state, forces,
+                       snapshot, w->snapDoubles, gradNext, gradState, gradForces, rows, ws, wsDoubles, gradMasses,
+                       fcMode, massParams, w->deferRows, bodyInertia);
+    return hipGetLastError();
+  }
   hipLaunchKernelGGL(nimble_backward_kernel, dim3(grid), dim3(64), lds, st, w->dev, batch, state, forces, snapshot,
                      w->snapDoubles, gradNext, gradState, gradForces, rows, ws, wsDoubles, gradMasses, fcMode,
                      massParams, w->deferRows);
@@ -553,39 +596,60 @@ static hipError_t launchBackward(nimble_world_t w, int grid, hipStream_t st, int
 int nimble_backward(nimble_world_t w, int32_t batch, const double* state, const double* forces,
                     double* snapshot, const double* grad_next_state, double* grad_state,
                     double* grad_forces, void* stream) {
+  return nimble_backward_pw(w, batch, state, forces, snapshot, grad_next_state, grad_state, grad_forces, nullptr,
+                            stream);
+}
+
+int nimble_backward_pw(nimble_world_t w, int32_t batch, const double* state, const double* forces,
+                       double* snapshot, const double* grad_next_state, double* grad_state,
+                       double* grad_forces, const double* body_inertia, void* stream) {
   if (!w || batch < 0) return fail(NIMBLE_ERR_INVALID, "bad arguments");
   if (batch == 0) return NIMBLE_OK;
   if (!state || !forces || !grad_next_state || !grad_state || !grad_forces || !snapshot)
     return fail(NIMBLE_ERR_INVALID, "null buffer");
   hipStream_t st = (hipStream_t)stream;
   HIP_TRY(launchBackward(w, gridFor(batch), st, batch, state, forces, snapshot, grad_next_state, grad_state,
-                        grad_forces, 1, nullptr, 0, nullptr, 0, 1));
+                        grad_forces, 1, nullptr, 0, nullptr, 0, 1, body_inertia));
   return NIMBLE_OK;
 }
 
 int nimble_backward_masses(nimble_world_t w, int32_t batch, const double* state, const double* forces,
                            double* snapshot, const double* grad_next_state, double* grad_state,
                            double* grad_forces, double* grad_masses, void* stream) {
+  return nimble_backward_masses_pw(w, batch, state, forces, snapshot, grad_next_state, grad_state, grad_forces,
+                                   grad_masses, nullptr, stream);
+}
+
+int nimble_backward_masses_pw(nimble_world_t w, int32_t batch, const double* state, const double* forces,
+                              double* snapshot, const double* grad_next_state, double* grad_state,
+                              double* grad_forces, double* grad_masses, const double* body_inertia, void* stream) {
   if (!w || batch < 0) return fail(NIMBLE_ERR_INVALID, "bad arguments");
   if (batch == 0) return NIMBLE_OK;
   if (!state || !forces || !grad_next_state || !grad_state || !grad_forces || !snapshot || !grad_masses)
     return fail(NIMBLE_ERR_INVALID, "null buffer");
   hipStream_t st = (hipStream_t)stream;
   HIP_TRY(launchBackward(w, gridFor(batch), st, batch, state, forces, snapshot, grad_next_state, grad_state,
-                        grad_forces, 1, nullptr, 0, grad_masses, 0, 1));
+                        grad_forces, 1, nullptr, 0, grad_masses, 0, 1, body_inertia));
   return NIMBLE_OK;
 }
 
 int nimble_backward_inertia(nimble_world_t w, int32_t batch, const double* state, const double* forces,
                             double* snapshot, const double* grad_next_state, double* grad_state,
                             double* grad_forces, double* grad_inertia, void* stream) {
+  return nimble_backward_inertia_pw(w, batch, state, forces, snapshot, grad_next_state, grad_state, grad_forces,
+                                    grad_inertia, nullptr, stream);
+}
+
+int nimble_backward_inertia_pw(nimble_world_t w, int32_t batch, const double* state, const double* forces,
+                               double* snapshot, const double* grad_next_state, double* grad_state,
+                               double* grad_forces, double* grad_inertia, const double* body_inertia, void* stream) {
   if (!w || batch < 0) return fail(NIMBLE_ERR_INVALID, "bad arguments");
   if (batch == 0) return NIMBLE_OK;
   if (!state || !forces || !grad_next_state || !grad_state || !grad_forces || !snapshot || !grad_inertia)
     return fail(NIMBLE_ERR_INVALID, "null buffer");
   hipStream_t st = (hipStream_t)stream;
   HIP_TRY(launchBackward(w, gridFor(batch), st, batch, state, forces, snapshot, grad_next_state, grad_state,
-                        grad_forces, 1, nullptr, 0, grad_inertia, 0, 10));
+                        grad_forces, 1, nullptr, 0, grad_inertia, 0, 10, body_inertia));
   return NIMBLE_OK;
 }
 
@@ -607,6 +671,13 @@ int64_t nimble_jacobian_workspace_doubles(nimble_world_t w, int32_t batch) {
 int nimble_jacobians(nimble_world_t w, int32_t batch, const double* state, const double* forces,
                      const double* snapshot, double* state_jacobian, double* force_jacobian, double* workspace,
                      void* stream) {
+  return nimble_jacobians_pw(w, batch, state, forces, snapshot, state_jacobian, force_jacobian, workspace, nullptr,
+                             stream);
+}
+
+int nimble_jacobians_pw(nimble_world_t w, int32_t batch, const double* state, const double* forces,
+                        const double* snapshot, double* state_jacobian, double* force_jacobian, double* workspace,
+                        const double* body_inertia, void* stream) {
   if (!w || batch < 0) return fail(NIMBLE_ERR_INVALID, "bad arguments");
   if (batch == 0 || w->host.n == 0) return NIMBLE_OK;
   if (!state || !forces || !snapshot || !state_jacobian || !force_jacobian)
@@ -619,13 +690,20 @@ int nimble_jacobians(nimble_world_t w, int32_t batch, const double* state, const
   hipStream_t st = (hipStream_t)stream;
   HIP_TRY(launchBackward(w, grid, st, batch, state, forces, const_cast<double*>(snapshot), nullptr, state_jacobian,
                         force_jacobian, rows, w->jacWsDoubles > 0 ? workspace : nullptr, w->jacWsDoubles, nullptr, 0,
-                        1));
+                        1, body_inertia));
   return NIMBLE_OK;
 }
 
 int nimble_constraint_force_jacobians(nimble_world_t w, int32_t batch, const double* state, const double* forces,
                                       const double* snapshot, double* dfc_dstate, double* dfc_dforces,
                                       double* workspace, void* stream) {
+  return nimble_constraint_force_jacobians_pw(w, batch, state, forces, snapshot, dfc_dstate, dfc_dforces, workspace,
+                                              nullptr, stream);
+}
+
+int nimble_constraint_force_jacobians_pw(nimble_world_t w, int32_t batch, const double* state, const double* forces,
+                                         const double* snapshot, double* dfc_dstate, double* dfc_dforces,
+                                         double* workspace, const double* body_inertia, void* stream) {
   if (!w || batch < 0) return fail(NIMBLE_ERR_INVALID, "bad arguments");
   if (batch == 0 || w->host.n == 0) return NIMBLE_OK;
   if (!state || !forces || !snapshot || !dfc_dstate || !dfc_dforces) return fail(NIMBLE_ERR_INVALID, "null buffer");
@@ -636,7 +714,8 @@ int nimble_constraint_force_jacobians(nimble_world_t w, int32_t batch, const dou
   const int grid = items < JAC_GRID ? (int)items : JAC_GRID;
   hipStream_t st = (hipStream_t)stream;
   HIP_TRY(launchBackward(w, grid, st, batch, state, forces, const_cast<double*>(snapshot), nullptr, dfc_dstate,
-                        dfc_dforces, rows, w->jacWsDoubles > 0 ? workspace : nullptr, w->jacWsDoubles, nullptr, 1, 1));
+                        dfc_dforces, rows, w->jacWsDoubles > 0 ? workspace : nullptr, w->jacWsDoubles, nullptr, 1, 1,
+                        body_inertia));
   return NIMBLE_OK;
 }
 

@@ -25,6 +25,7 @@
 #include "pool_sizes.h"
 #include "capsule.cuh"
 #include "mesh.cuh"
+#include "inertia.cuh"
 
 #define CT_FACE_VERTEX 1
 #define CT_VERTEX_FACE 2
@@ -4190,25 +4191,29 @@ __device__ __forceinline__ double mFieldPasses(const ModelDev& md, const double*
 
 // `buf` holds 24 nb doubles and `wI` 13 nb; with `fuse` (two pairs per pass)
 // `buf` holds 48 nb.  NV: the pairs' columns 0..7, leading dimension ldNV.
+// kPW: the bodies' parameters from the world's array `bi` (inertia.cuh).
+// (`bi`: that world's [nb][10] block of body_inertia; unused otherwise)
+template <bool kPW = false>
 __device__ double mFieldsTerm(const ModelDev& md, double* s, const Layout& L, const double* NV, int ldNV, double* buf,
-                              double* wI, bool fuse, int lane, int k, const double* Z, double coefDelta, double imp
+                              double* wI, bool fuse, int lane, int k, const double* Z, double coefDelta, double imp,
 #ifdef NIMBLE_STAGE_TIMING
-                              , double* g_stamp
+                              double* g_stamp,
 #endif
-) {
+                              const double* bi = nullptr) {
   const int nb = md.nb;
   const double coef[4] = {coefDelta, 1.0, -imp, -imp};
   if (lane < nb) {
     // worldInertia's arithmetic, stored compactly
     const int b = lane;
     const double* Tw = s + L.Tw + 12 * b;
-    const double m = md.mass[b];
+    const BodyInertia<kPW> P(md, bi, b);
+    const double m = P.mass();
     double cw[3], Rc[9], tmp[9];
     for (int r = 0; r < 3; r++)
-      cw[r] = Tw[r * 4] * md.com[b][0] + Tw[r * 4 + 1] * md.com[b][1] + Tw[r * 4 + 2] * md.com[b][2] + Tw[r * 4 + 3];
+      cw[r] = Tw[r * 4] * P.com(0) + Tw[r * 4 + 1] * P.com(1) + Tw[r * 4 + 2] * P.com(2) + Tw[r * 4 + 3];
     for (int r = 0; r < 3; r++)
       for (int c = 0; c < 3; c++)
-        tmp[r * 3 + c] = Tw[r * 4] * md.Ic[b][c] + Tw[r * 4 + 1] * md.Ic[b][3 + c] + Tw[r * 4 + 2] * md.Ic[b][6 + c];
+        tmp[r * 3 + c] = Tw[r * 4] * P.Ic(c) + Tw[r * 4 + 1] * P.Ic(3 + c) + Tw[r * 4 + 2] * P.Ic(6 + c);
     for (int r = 0; r < 3; r++)
       for (int c = 0; c < 3; c++)
         Rc[r * 3 + c] = tmp[r * 3] * Tw[c * 4] + tmp[r * 3 + 1] * Tw[c * 4 + 1] + tmp[r * 3 + 2] * Tw[c * 4 + 2];

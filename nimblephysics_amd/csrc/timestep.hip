@@ -23,8 +23,32 @@
 #include "wave.cuh"
 #include "stamp.cuh"
 #include "chol_wave.cuh"
+#include "inertia.cuh"
 
 #define WAVE 64
+
+// Two translation units hold this file's kernels.  Compiled as it is, it gives
+// the kernels that read every body's inertial parameters from the shared
+// device model; timestep_pw.hip includes it with NIMBLE_PER_WORLD_KERNELS
+// defined and gives the instances that read them from the per-world array
+// (body_inertia, inertia.cuh) instead.  Everything below the kernels is
+// inlined into them on cost, and the inliner's cost of a function depends on
+// how many callers the code object has: with both sets in one code object
+// nimble_backward_wide_kernel came out scheduled differently from the
+// library without the per-world path (the other four were the same), apart
+// they are instruction for instruction what they were.  A host build (the
+// wavefront emulation of tests/cpp/wave_emu, one translation unit with
+// capi.cpp) has no code object to keep apart and takes both sets.
+#if defined(NIMBLE_PER_WORLD_KERNELS)
+#define NIMBLE_SHARED_MODEL_INSTANCES 0
+#define NIMBLE_PER_WORLD_INSTANCES 1
+#elif defined(__HIP__)
+#define NIMBLE_SHARED_MODEL_INSTANCES 1
+#define NIMBLE_PER_WORLD_INSTANCES 0
+#else
+#define NIMBLE_SHARED_MODEL_INSTANCES 1
+#define NIMBLE_PER_WORLD_INSTANCES 1
+#endif
 
 // ---------------------------------------------------------------------------
 // Forward kinematics + velocities + velocity-product (bias) accelerations.
@@ -168,15 +192,19 @@ __device__ __forceinline__ void ancestorAccelerations(const ModelDev& md, double
 }
 
 // World-frame spatial inertia of body b (6x6, row-major) at the world origin.
-// dart/dynamics/Inertia.cpp:1368 computeSpatialTensor in world axes.
-__device__ __forceinline__ void worldInertia(const ModelDev& md, const double* Tw, int b, double* I) {
-  const double m = md.mass[b];
+// dart/dynamics/Inertia.cpp:1368 computeSpatialTensor in world axes.  kPW: the
+// body's parameters come from the world's own array `bi` (inertia.cuh
+// BodyInertia), loaded here, at the point of use.
+template <bool kPW = false>
+__device__ __forceinline__ void worldInertia(const ModelDev& md, const double* bi, const double* Tw, int b, double* I) {
+  const BodyInertia<kPW> P(md, bi, b);
+  const double m = P.mass();
   double cw[3], Rc[9], tmp[9];
-  for (int r = 0; r < 3; r++) cw[r] = Tw[r * 4] * md.com[b][0] + Tw[r * 4 + 1] * md.com[b][1] + Tw[r * 4 + 2] * md.com[b][2] + Tw[r * 4 + 3];
+  for (int r = 0; r < 3; r++) cw[r] = Tw[r * 4] * P.com(0) + Tw[r * 4 + 1] * P.com(1) + Tw[r * 4 + 2] * P.com(2) + Tw[r * 4 + 3];
   // R Ic R^T
   for (int r = 0; r < 3; r++)
     for (int c = 0; c < 3; c++)
-      tmp[r * 3 + c] = Tw[r * 4] * md.Ic[b][c] + Tw[r * 4 + 1] * md.Ic[b][3 + c] + Tw[r * 4 + 2] * md.Ic[b][6 + c];
+      tmp[r * 3 + c] = Tw[r * 4] * P.Ic(c) + Tw[r * 4 + 1] * P.Ic(3 + c) + Tw[r * 4 + 2] * P.Ic(6 + c);
   for (int r = 0; r < 3; r++)
     for (int c = 0; c < 3; c++)
       Rc[r * 3 + c] = tmp[r * 3] * Tw[c * 4] + tmp[r * 3 + 1] * Tw[c * 4 + 1] + tmp[r * 3 + 2] * Tw[c * 4 + 2];
@@ -195,12 +223,14 @@ __device__ __forceinline__ void worldInertia(const ModelDev& md, const double* T
 // Composite inertias IC[b] (subtree sums) and bias forces F[b] = sum over the
 // subtree of  I_i (A_i - a_g) + V_i x* (I_i V_i)  -- the world-frame
 // restatement of BodyNode::updateTransmittedForceID (BodyNode.cpp:1994).
-__device__ __forceinline__ void composites(const ModelDev& md, double* s, const Layout& L, int lane) {
+template <bool kPW = false>
+__device__ __forceinline__ void composites(const ModelDev& md, double* s, const Layout& L, int lane,
+                                           const double* bi = nullptr) {
   const double ag[6] = {0, 0, 0, md.g[0], md.g[1], md.g[2]};
   if (lane < md.nb) {
     const int b = lane;
     double* I = s + L.IC + 36 * b;
-    worldInertia(md, s + L.Tw + 12 * b, b, I);
+    worldInertia<kPW>(md, bi, s + L.Tw + 12 * b, b, I);
     double u[6], h[6], f[6], vxh[6];
     for (int i = 0; i < 6; i++) u[i] = s[L.A + 6 * b + i] - ag[i];
     mv6(I, u, f);
@@ -336,12 +366,15 @@ __device__ __forceinline__ void coreDynamics(const ModelDev& md, double* s, cons
 // leaves a world whose LCP has more than `deferRows` rows (> 64: more than
 // 21 frictional contacts) to the R = 2 kernel launched after it, which
 // steps only those worlds, from the same inputs.
-template <int R, bool kMesh = false>
+// kPW: the world's bodies take their inertial parameters from its rows of
+// `bodyInertia` ([batch][nb][10], inertia.cuh) instead of the model.
+template <int R, bool kMesh = false, bool kPW = false>
 __device__ __forceinline__ void forwardWorld(const ModelDev* __restrict__ mdp, const Layout& L,
                                              const double* __restrict__ state, const double* __restrict__ forces,
                                              double* __restrict__ lcpCache, double* __restrict__ nextState,
                                              double* __restrict__ snapshot, int snapDoubles, int cacheDoubles,
-                                             int deferRows, int env, bool deferLists) {
+                                             int deferRows, int env, bool deferLists,
+                                             const double* __restrict__ bodyInertia = nullptr) {
   extern __shared__ double s[];
   const ModelDev& md = *mdp;
   const int lane = threadIdx.x & (WAVE - 1);
@@ -435,7 +468,7 @@ __device__ __forceinline__ void forwardWorld(const ModelDev* __restrict__ mdp, c
     // body transforms final: the helper wave detects the contacts meanwhile
     if (helperOn) collidePost(lds<true>(s) + L.ct, CS_GO, lane);
     STAMP(14);
-    composites(md, s, L, lane);
+    composites<kPW>(md, s, L, lane, kPW ? bodyInertia + (size_t)env * md.nb * 10 : nullptr);
     STAMP(15);
     massMatrixAndBias(md, s, L, lane, s + L.rhs);
     STAMP(16);
@@ -514,6 +547,7 @@ __device__ __forceinline__ void forwardWorld(const ModelDev* __restrict__ mdp, c
   }
 }
 
+#if NIMBLE_SHARED_MODEL_INSTANCES
 extern "C" __global__ void __launch_bounds__(2 * WAVE) __attribute__((amdgpu_waves_per_eu(2)))
 nimble_forward_kernel(const ModelDev* __restrict__ mdp, Layout L, const double* __restrict__ state,
                       const double* __restrict__ forces, double* __restrict__ lcpCache,
@@ -537,7 +571,34 @@ nimble_forward_mesh_kernel(const ModelDev* __restrict__ mdp, Layout L, const dou
   forwardWorld<1, true>(mdp, L, state, forces, lcpCache, nextState, snapshot, snapDoubles, cacheDoubles, deferRows,
                         blockIdx.x, deferLists != 0);
 }
+#endif  // NIMBLE_SHARED_MODEL_INSTANCES
 
+#if NIMBLE_PER_WORLD_INSTANCES
+// the two one-row instances with per-world body inertial parameters
+// (nimble_forward_pw): bodyInertia [gridDim.x][nb][10].  The wide kernel
+// below serves them as well: it reloads the dynamics cache these stored and
+// recomputes no inertia.
+extern "C" __global__ void __launch_bounds__(2 * WAVE) __attribute__((amdgpu_waves_per_eu(2)))
+nimble_forward_pw_kernel(const ModelDev* __restrict__ mdp, Layout L, const double* __restrict__ state,
+                         const double* __restrict__ forces, double* __restrict__ lcpCache,
+                         double* __restrict__ nextState, double* __restrict__ snapshot, int snapDoubles,
+                         int cacheDoubles, int deferRows, int deferLists, const double* __restrict__ bodyInertia) {
+  forwardWorld<1, false, true>(mdp, L, state, forces, lcpCache, nextState, snapshot, snapDoubles, cacheDoubles,
+                               deferRows, blockIdx.x, deferLists != 0, bodyInertia);
+}
+
+extern "C" __global__ void __launch_bounds__(2 * WAVE) __attribute__((amdgpu_waves_per_eu(2)))
+nimble_forward_mesh_pw_kernel(const ModelDev* __restrict__ mdp, Layout L, const double* __restrict__ state,
+                              const double* __restrict__ forces, double* __restrict__ lcpCache,
+                              double* __restrict__ nextState, double* __restrict__ snapshot, int snapDoubles,
+                              int cacheDoubles, int deferRows, int deferLists,
+                              const double* __restrict__ bodyInertia) {
+  forwardWorld<1, true, true>(mdp, L, state, forces, lcpCache, nextState, snapshot, snapDoubles, cacheDoubles,
+                              deferRows, blockIdx.x, deferLists != 0, bodyInertia);
+}
+#endif  // NIMBLE_PER_WORLD_INSTANCES
+
+#if NIMBLE_SHARED_MODEL_INSTANCES
 // the worlds nimble_forward_kernel deferred (snapshot status ST_DEFERRED),
 // from the one-row kernel's dynamics and contacts: up to 64 LCP rows with the
 // pool in the big LDS stage (the one-row code, the helper wave on the task
@@ -574,6 +635,7 @@ nimble_forward_wide_kernel(const ModelDev* __restrict__ mdp, Layout L, const dou
   forwardWorld<2>(mdp, L, state, forces, lcpCache, nextState, snapshot, snapDoubles, cacheDoubles, 1 << 30, env,
                   false);
 }
+#endif  // NIMBLE_SHARED_MODEL_INSTANCES
 
 // posPos^T gp and velPos^T gp of one free (ND = 6) or ball (ND = 3) joint at
 // dof offset o, added to lane k's gq / gvOut: 4 ND lanes run one perturbed
@@ -630,7 +692,9 @@ __device__ __forceinline__ void fdBlocksVjp(const double* s, const Layout& L, in
 // (Skeleton::getJacobianOfID, DifferentiableContactConstraint / BackpropSnapshot
 // use) contracted with w, collapsed to O(nb) 6-vector work; the identity is
 // checked against central differences in tools/proto/adjoint_rnea.py.
-__device__ __forceinline__ void adjointVectors(const ModelDev& md, double* s, const Layout& L, int lane) {
+template <bool kPW = false>
+__device__ __forceinline__ void adjointVectors(const ModelDev& md, double* s, const Layout& L, int lane,
+                                               const double* bi = nullptr) {
   const double ag[6] = {0, 0, 0, md.g[0], md.g[1], md.g[2]};
   const int nb = md.nb, n = md.n;
   if (lane < nb) {
@@ -642,7 +706,7 @@ __device__ __forceinline__ void adjointVectors(const ModelDev& md, double* s, co
         for (int i = 0; i < 6; i++) W[i] += wk * s[L.Sw + 6 * k + i];
       }
     double I[36];
-    worldInertia(md, s + L.Tw + 12 * b, b, I);
+    worldInertia<kPW>(md, bi, s + L.Tw + 12 * b, b, I);
     const double* V = s + L.V + 6 * b;
     double u[6], p[6], h[6], t[6], t2[6], VxW[6];
     for (int i = 0; i < 6; i++) u[i] = s[L.A + 6 * b + i] - ag[i];
@@ -729,14 +793,18 @@ __device__ void rightJacobianCol(const double* th, int k, double* o) {
 // mode only replaces u = A_c_ub_E^T Minv gv by e_r (and gv, gp by 0).
 // R row slots per lane: the R = 1 kernel takes the items of worlds with at
 // most `deferRows` LCP rows, the R = 2 kernel the others.
-template <int R>
+// kPW: item (world, row) reads its world's rows of `bodyInertia`
+// ([batch][nb][10], inertia.cuh) wherever the model's mass, COM and moment
+// are read otherwise.
+template <int R, bool kPW = false>
 __device__ __forceinline__ void backwardItems(const ModelDev* __restrict__ mdp, int batch,
                                               const double* __restrict__ state, const double* __restrict__ forces,
                                               double* __restrict__ snapshot, int snapDoubles,
                                               const double* __restrict__ gradNext, double* __restrict__ gradState,
                                               double* __restrict__ gradForces, int rows, double* __restrict__ ws,
                                               int wsDoubles, double* __restrict__ gradMasses, int fcMode,
-                                              int massParams, int deferRows) {
+                                              int massParams, int deferRows,
+                                              const double* __restrict__ bodyInertia = nullptr) {
   extern __shared__ double s[];
   const ModelDev& md = *mdp;
   const Layout& L = md.lay[1];
@@ -775,6 +843,7 @@ __device__ __forceinline__ void backwardItems(const ModelDev* __restrict__ mdp, 
         s[L.gv + i] = n + i == unitRow ? 1.0 : 0.0;
       }
     }
+    const double* bi = kPW ? bodyInertia + (size_t)env * md.nb * 10 : nullptr;
     double* sn = snapshot + (size_t)env * snapDoubles;
     double* hbmWs = ws != nullptr ? ws + (size_t)blockIdx.x * wsDoubles : sn + snapWorkspaceOffset(n);
     dynCacheCopy(md, s, L, sn + L.snDyn, false, lane);  // the forward's kinematics, L, C
@@ -817,7 +886,7 @@ __device__ __forceinline__ void backwardItems(const ModelDev* __restrict__ mdp, 
     }
     STAMP(22);
     accelerations(md, s, L, lane, x, s + L.adj);  // A = accelerations at a* (adjoint area not yet in use)
-    adjointVectors(md, s, L, lane);
+    adjointVectors<kPW>(md, s, L, lane, bi);
     STAMP(23);
 
     // ---- per-direction columns -------------------------------------------
@@ -928,9 +997,9 @@ __device__ __forceinline__ void backwardItems(const ModelDev* __restrict__ mdp, 
         }
       }
 #ifdef NIMBLE_STAGE_TIMING
-      const double mterm = mFieldsTerm(md, s, L, NVf, ldNV, buf, wI, mfuse, lane, k, Z, -dt, (double)imp, g_stamp);
+      const double mterm = mFieldsTerm<kPW>(md, s, L, NVf, ldNV, buf, wI, mfuse, lane, k, Z, -dt, (double)imp, g_stamp, bi);
 #else
-      const double mterm = mFieldsTerm(md, s, L, NVf, ldNV, buf, wI, mfuse, lane, k, Z, -dt, (double)imp);
+      const double mterm = mFieldsTerm<kPW>(md, s, L, NVf, ldNV, buf, wI, mfuse, lane, k, Z, -dt, (double)imp, bi);
 #endif
       TACC_END(81, tM);
       if (k < n) {
@@ -958,10 +1027,14 @@ __device__ __forceinline__ void backwardItems(const ModelDev* __restrict__ mdp, 
       if (lane < md.nb) {
         const int b = lane;
         const double* Tw = s + L.Tw + 12 * b;
-        const double m = md.mass[b];
+        // (the body's mass and local COM: the world's own, or the model's;
+        // plain selects: through BodyInertia the shared-model kernels'
+        // register allocation came out different from what it was)
+        const double m = kPW ? bi[10 * b] : md.mass[b];
+        const double* cb = kPW ? bi + 10 * b + 1 : md.com[b];
         double cw[3];
         for (int r = 0; r < 3; r++)
-          cw[r] = Tw[r * 4] * md.com[b][0] + Tw[r * 4 + 1] * md.com[b][1] + Tw[r * 4 + 2] * md.com[b][2] + Tw[r * 4 + 3];
+          cw[r] = Tw[r * 4] * cb[0] + Tw[r * 4 + 1] * cb[1] + Tw[r * 4 + 2] * cb[2] + Tw[r * 4 + 3];
         auto comVel = [&](const double* y, double* u) {
           double cx[3];
           cross3(cw, y, cx);  // c x y_ang
@@ -1081,6 +1154,7 @@ __device__ __forceinline__ void backwardItems(const ModelDev* __restrict__ mdp, 
   }
 }
 
+#if NIMBLE_SHARED_MODEL_INSTANCES
 extern "C" __global__ void __launch_bounds__(WAVE)
 nimble_backward_kernel(const ModelDev* __restrict__ mdp, int batch, const double* __restrict__ state,
                        const double* __restrict__ forces, double* __restrict__ snapshot, int snapDoubles,
@@ -1100,3 +1174,31 @@ nimble_backward_wide_kernel(const ModelDev* __restrict__ mdp, int batch, const d
   backwardItems<2>(mdp, batch, state, forces, snapshot, snapDoubles, gradNext, gradState, gradForces, rows, ws,
                    wsDoubles, gradMasses, fcMode, massParams, deferRows);
 }
+#endif  // NIMBLE_SHARED_MODEL_INSTANCES
+
+#if NIMBLE_PER_WORLD_INSTANCES
+// the backward kernels with per-world body inertial parameters
+// (nimble_backward_pw and the other _pw entry points): bodyInertia
+// [batch][nb][10], indexed by the item's world
+extern "C" __global__ void __launch_bounds__(WAVE)
+nimble_backward_pw_kernel(const ModelDev* __restrict__ mdp, int batch, const double* __restrict__ state,
+                          const double* __restrict__ forces, double* __restrict__ snapshot, int snapDoubles,
+                          const double* __restrict__ gradNext, double* __restrict__ gradState,
+                          double* __restrict__ gradForces, int rows, double* __restrict__ ws, int wsDoubles,
+                          double* __restrict__ gradMasses, int fcMode, int massParams, int deferRows,
+                          const double* __restrict__ bodyInertia) {
+  backwardItems<1, true>(mdp, batch, state, forces, snapshot, snapDoubles, gradNext, gradState, gradForces, rows, ws,
+                         wsDoubles, gradMasses, fcMode, massParams, deferRows, bodyInertia);
+}
+
+extern "C" __global__ void __launch_bounds__(WAVE)
+nimble_backward_wide_pw_kernel(const ModelDev* __restrict__ mdp, int batch, const double* __restrict__ state,
+                               const double* __restrict__ forces, double* __restrict__ snapshot, int snapDoubles,
+                               const double* __restrict__ gradNext, double* __restrict__ gradState,
+                               double* __restrict__ gradForces, int rows, double* __restrict__ ws, int wsDoubles,
+                               double* __restrict__ gradMasses, int fcMode, int massParams, int deferRows,
+                               const double* __restrict__ bodyInertia) {
+  backwardItems<2, true>(mdp, batch, state, forces, snapshot, snapDoubles, gradNext, gradState, gradForces, rows, ws,
+                         wsDoubles, gradMasses, fcMode, massParams, deferRows, bodyInertia);
+}
+#endif  // NIMBLE_PER_WORLD_INSTANCES

@@ -53,8 +53,11 @@ class LossGradientHighLevelAPI:
 class BackpropSnapshot:
     """The batched BackpropSnapshot of one forward launch over B worlds."""
 
-    def __init__(self, world: World, dev, state, forces, next_state, snapshot, single: bool):
+    def __init__(self, world: World, dev, state, forces, next_state, snapshot, single: bool, body_inertia=None):
         self._world = world
+        # the step's per-world body parameters ([B, num_bodies, 10], or None
+        # for the model's own): every derivative of the step reads them again
+        self._inertia = body_inertia
         self._dev = dev
         # copies: the caller may reuse or update its state / action buffers in
         # place before the lazily computed Jacobians and backprop read them
@@ -83,7 +86,8 @@ class BackpropSnapshot:
         if self._jac is None:
             with torch.cuda.device(self._state.device):
                 stream = torch.cuda.current_stream(self._state.device).cuda_stream
-                self._jac = self._dev.jacobians(self._state, self._forces, self._snap, stream)
+                self._jac = self._dev.jacobians(self._state, self._forces, self._snap, stream,
+                                                    body_inertia=self._inertia)
         return self._jac
 
     # --- Jacobians (BackpropSnapshot.cpp) ---------------------------------------
@@ -162,7 +166,8 @@ class BackpropSnapshot:
         if self._fcjac is None:
             with torch.cuda.device(self._state.device):
                 stream = torch.cuda.current_stream(self._state.device).cuda_stream
-                self._fcjac = self._dev.constraint_force_jacobians(self._state, self._forces, self._snap, stream)
+                self._fcjac = self._dev.constraint_force_jacobians(self._state, self._forces, self._snap, stream,
+                                                                       body_inertia=self._inertia)
         Js, Jf = self._fcjac
         n = self._n
         J = {"POSITION": Js[:, :, :n], "VELOCITY": Js[:, :, n:], "FORCE": Jf}.get(kind)
@@ -185,9 +190,10 @@ class BackpropSnapshot:
             stream = torch.cuda.current_stream(self._state.device).cuda_stream
             if self._world.getMassDims() > 0:
                 gm = mass_gradient(self._dev, self._world._mass_selection(), self._state, self._forces, self._snap, g,
-                                   gs, gf, stream)
+                                   gs, gf, stream, self._inertia)
             else:
-                self._dev.backward(self._state, self._forces, self._snap, g, gs, gf, stream)
+                extra = () if self._inertia is None else (self._inertia,)
+                self._dev.backward(self._state, self._forces, self._snap, g, gs, gf, stream, *extra)
                 gm = torch.zeros((B, 0), dtype=torch.float64, device=self._state.device)
         return gs, gf, gm
 
@@ -260,7 +266,7 @@ class BackpropSnapshot:
         return self._out(self._dev.status(self._snap))
 
 
-def forwardPass(world: World, idempotent: bool = False, state=None, action=None) -> BackpropSnapshot:
+def forwardPass(world: World, idempotent: bool = False, state=None, action=None, mass=None) -> BackpropSnapshot:
     """neural::forwardPass (NeuralUtils.cpp:26).
 
     ``forwardPass(world)`` steps the world's own state and control forces (the
@@ -268,7 +274,13 @@ def forwardPass(world: World, idempotent: bool = False, state=None, action=None)
     control forces are cleared, unless ``idempotent``, which restores the
     pre-step state).  ``forwardPass(world, state=S, action=A)`` with device
     tensors [B, 2n] / [B, |A|] steps B worlds and leaves the world object
-    untouched."""
+    untouched.  The batched form takes ``mass``, a [B, getMassDims()] tensor
+    of per-world tuned values (see timestep): the snapshot keeps the expanded
+    parameter array, its Jacobians and backprop are those of each world's own
+    parameters, and its lossWrtMass is [B, getMassDims()]."""
+    bi = None
+    if mass is not None and (state is None or state.dim() != 2):
+        raise ValueError("forwardPass: a per-world mass needs the batched (2-D) state and action")
     if state is None:
         single = True
         dev = _compute_device(torch.zeros(0))
@@ -286,11 +298,16 @@ def forwardPass(world: World, idempotent: bool = False, state=None, action=None)
             raise RuntimeError("batched forwardPass takes device tensors")
         dev = st.device
         st, act = st.contiguous(), act.contiguous()
+        if mass is not None:
+            if mass.dim() != 2 or mass.shape[0] != st.shape[0] or mass.shape[1] != world.getMassDims():
+                raise ValueError(f"per-world mass must be [{st.shape[0]}, {world.getMassDims()}] (batch, the world's "
+                                 f"tuned mass dims), got {tuple(mass.shape)}")
+            bi = world._batched_inertia(mass.detach().to(dev, torch.float64))
     prev = getattr(world, "_batch_state", None)
     saved = prev.cache.clone() if (idempotent and prev is not None) else None
     try:
         with torch.cuda.device(dev):
-            devworld, forces, nxt, snap = step_batch(world, st, act)
+            devworld, forces, nxt, snap = step_batch(world, st, act, bi)
     finally:
         if idempotent:
             # RestorableSnapshot: the LCP warm-start cache is part of the world
@@ -305,6 +322,6 @@ def forwardPass(world: World, idempotent: bool = False, state=None, action=None)
         out = nxt[0].cpu().numpy()
         world.setState(out)
         world.setControlForces(np.zeros(world.getNumDofs()))
-    snapshot = BackpropSnapshot(world, devworld, st, forces, nxt, snap, single)
+    snapshot = BackpropSnapshot(world, devworld, st, forces, nxt, snap, single, bi)
     world._cached_snapshot = snapshot
     return snapshot

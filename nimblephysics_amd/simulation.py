@@ -197,7 +197,9 @@ class World:
     # them into the bodies (the device model is rebuilt on the next step);
     # lossWrtMass comes from nimble_backward_masses (masses only) or
     # nimble_backward_inertia (all ten parameters per body) through
-    # _mass_selection().
+    # _mass_selection().  One mass vector per world of a batch never reaches
+    # the bodies: _batched_inertia() expands the rows to the kernels'
+    # per-world parameter array on the device.
     MASS_ENTRY_DIMS = {"INERTIA_MASS": 1, "INERTIA_COM": 3, "INERTIA_COM_MU": 1, "INERTIA_DIAGONAL": 3,
                        "INERTIA_OFF_DIAGONAL": 3, "INERTIA_FULL": 10}
 
@@ -301,6 +303,58 @@ class World:
                 S[base + 1:base + 4, col] = b.getBeta()
                 col += 1
         return False, S
+
+    def _body_inertia_base(self) -> np.ndarray:
+        """The model's own parameters as the per-world array's rows: [nb, 10]
+        in INERTIA_FULL order per device body (mass, local COM, Ixx Iyy Izz
+        Ixy Ixz Iyz; zeros for the massless frames of compound-joint chains),
+        the values desc_arrays() uploads."""
+        rows = [np.concatenate([[b.mass], b.com, b.moment]) if b is not None else np.zeros(10)
+                for _, _, b, _, _ in self._model_bodies()]
+        return np.asarray(rows, dtype=np.float64).reshape(len(rows), 10)
+
+    def _batched_inertia(self, mass2d):
+        """[B, getMassDims()] mass vectors (one per world, World::getMasses
+        order) -> the per-world parameter array [B, nb, 10] of
+        nimble_forward_pw, on mass2d's device with torch ops only: every world
+        starts from the model's values and has its tuned components
+        overwritten through _mass_selection() -- a one-hot column copies the
+        value, an INERTIA_COM_MU column writes beta * mu into the COM, as
+        setMasses does; where two entries tune one component the later entry
+        wins, as in setMasses.  The world's bodies are not touched and
+        nothing is copied back to the host."""
+        import torch
+        D = self.getMassDims()
+        if mass2d.dim() != 2 or mass2d.shape[1] != D:
+            raise ValueError(f"mass must be [batch, {D}] (the world's tuned mass dims), got {tuple(mass2d.shape)}")
+        key = (self._version, tuple((id(b), k) for b, k, _, _ in self._mass_tuned), mass2d.device)
+        cached = getattr(self, "_batched_inertia_plan", None)
+        if cached is None or cached[0] != key:
+            base = self._body_inertia_base()
+            only_masses, sel = self._mass_selection()
+            if only_masses:
+                rows, cols, coef = [10 * i for i in sel], list(range(D)), [1.0] * D
+            else:
+                # column by column, so that a component tuned twice keeps the
+                # later entry's value
+                last = {}
+                for c in range(D):
+                    for r in np.nonzero(sel[:, c])[0]:
+                        last[int(r)] = (c, float(sel[r, c]))
+                rows = sorted(last)
+                cols = [last[r][0] for r in rows]
+                coef = [last[r][1] for r in rows]
+            dev = mass2d.device
+            cached = (key, torch.as_tensor(base.reshape(-1), dtype=torch.float64).to(dev),
+                      torch.tensor(rows, dtype=torch.long).to(dev), torch.tensor(cols, dtype=torch.long).to(dev),
+                      torch.tensor(coef, dtype=torch.float64).to(dev))
+            self._batched_inertia_plan = cached
+        _, base, rows, cols, coef = cached
+        B = mass2d.shape[0]
+        out = base.unsqueeze(0).repeat(B, 1)
+        if rows.numel() > 0:
+            out[:, rows] = mass2d.detach().to(torch.float64).index_select(1, cols) * coef
+        return out.reshape(B, -1, 10)
 
     def _model_bodies(self):
         """The device model's bodies in order: (skeleton index, skeleton,

@@ -29,6 +29,17 @@ World::setMasses before the step): 1-D, shared by every world of the batch
 (the device model is rebuilt when it changes).  Its gradient is lossWrtMass
 (BackpropSnapshot::getMassVelJacobian^T dL/dv', nimble_backward_masses),
 summed over the batch for a batched state.
+
+Per-world parameters: a 2-D ``mass`` of shape [B, getMassDims()] with a 2-D
+state and action gives world b the tuned values of row b (domain
+randomisation, batched system identification).  The rows are expanded on the
+device to the kernels' per-world parameter array (World._batched_inertia ->
+nimble_forward_pw's body_inertia); the world's bodies, ``getMasses()`` and the
+device model are left as they are, and nothing goes through the host.
+``mass.grad`` is then [B, getMassDims()], one row per world, not summed.
+Nothing is validated on the device: a non-positive mass or an indefinite
+moment of inertia gives whatever the arithmetic gives (usually NaN from the
+Cholesky factor), without an error.
 """
 from __future__ import annotations
 
@@ -120,11 +131,13 @@ def _check_status(world: World, dev, snap: torch.Tensor) -> None:
             f"their step would differ from the reference's (world.setStatusPolicy('record') to continue anyway)")
 
 
-def step_batch(world: World, st: torch.Tensor, act: torch.Tensor):
+def step_batch(world: World, st: torch.Tensor, act: torch.Tensor, body_inertia: Optional[torch.Tensor] = None):
     """One batched forward launch (neural::forwardPass on every row of the
     2-D device tensors `st` [B, 2n] / `act` [B, |action space|]).  Returns
     (device world, forces [B, n], next state [B, 2n], snapshot [B, S]); the
-    world's LCP warm-start caches advance and its status word is checked."""
+    world's LCP warm-start caches advance and its status word is checked.
+    `body_inertia` [B, num_bodies, 10]: per-world body parameters
+    (World._batched_inertia) instead of the model's."""
     B = st.shape[0]
     n = world.getNumDofs()
     if st.shape[1] != 2 * n:
@@ -142,25 +155,31 @@ def step_batch(world: World, st: torch.Tensor, act: torch.Tensor):
     nxt = torch.empty_like(st)
     snap = torch.empty((B, dev.snapshot_doubles), dtype=torch.float64, device=st.device)
     stream = torch.cuda.current_stream(st.device).cuda_stream
-    dev.forward(st, forces, bs.cache, nxt, snap, stream)
+    # (positional, and nothing extra on the shared path: callers may wrap the
+    # device world's forward / backward, as bench.py's kernel timer does)
+    if body_inertia is None:
+        dev.forward(st, forces, bs.cache, nxt, snap, stream)
+    else:
+        dev.forward(st, forces, bs.cache, nxt, snap, stream, body_inertia)
     world._last_snapshot = snap  # the batched BackpropSnapshot of this step
     _check_status(world, dev, snap)
     return dev, forces, nxt, snap
 
 
-def mass_gradient(dev, selection, st, forces, snap, g, gs, gf, stream):
+def mass_gradient(dev, selection, st, forces, snap, g, gs, gf, stream, body_inertia=None):
     """lossWrtMass [B, getMassDims()] (with the state / force gradients into
     gs / gf): nimble_backward_masses when only body masses are tuned, else
     nimble_backward_inertia's ten parameters per body taken to the mass
-    vector by World._mass_selection's matrix."""
+    vector by World._mass_selection's matrix.  `body_inertia`: the per-world
+    parameters of the forward that wrote `snap` (the _pw entry points)."""
     only_masses, sel = selection
     B = st.shape[0]
     if only_masses:
         gmb = torch.empty((B, dev.nb), dtype=torch.float64, device=st.device)
-        dev.backward_masses(st, forces, snap, g, gs, gf, gmb, stream)
+        dev.backward_masses(st, forces, snap, g, gs, gf, gmb, stream, body_inertia=body_inertia)
         return gmb.index_select(1, torch.tensor(sel, dtype=torch.long, device=st.device))
     gi = torch.empty((B, dev.nb, 10), dtype=torch.float64, device=st.device)
-    dev.backward_inertia(st, forces, snap, g, gs, gf, gi, stream)
+    dev.backward_inertia(st, forces, snap, g, gs, gf, gi, stream, body_inertia=body_inertia)
     return gi.reshape(B, dev.nb * 10) @ torch.as_tensor(sel, dtype=torch.float64, device=st.device)
 
 
@@ -170,7 +189,19 @@ class TimestepLayer(torch.autograd.Function):
         # `mass` follows the reference (timestep.py:34, world.setMasses): the
         # world's getMassDims() tuned body masses, one vector for the batch
         ctx.use_mass = mass is not None
-        if ctx.use_mass:
+        ctx.per_world = ctx.use_mass and mass.dim() == 2
+        if ctx.per_world:
+            # one row of tuned values per world: expanded on the device below,
+            # the world object and its device model stay as they are
+            if state.dim() != 2 or action.dim() != 2:
+                raise ValueError("a 2-D mass (one row per world) needs a 2-D state and action")
+            if mass.shape[0] != state.shape[0] or mass.shape[1] != world.getMassDims():
+                raise ValueError(f"per-world mass must be [{state.shape[0]}, {world.getMassDims()}] (batch, the "
+                                 f"world's tuned mass dims), got {tuple(mass.shape)}")
+            ctx.mass_shape = tuple(mass.shape)
+            ctx.mass_device = mass.device
+            ctx.mass_sel = world._mass_selection()
+        elif ctx.use_mass:
             if mass.dim() != 1 or mass.shape[0] != world.getMassDims():
                 raise ValueError(f"mass must be a vector of the world's {world.getMassDims()} tuned masses "
                                  f"(World::tuneMass), got shape {tuple(mass.shape)}")
@@ -194,7 +225,8 @@ class TimestepLayer(torch.autograd.Function):
             act = action.detach().reshape(1, -1) if squeeze else action.detach()
             st = st.contiguous()
             n = world.getNumDofs()
-            dev, forces, nxt, snap = step_batch(world, st, act)
+            bi = world._batched_inertia(mass.detach().to(cdev, torch.float64)) if ctx.per_world else None
+            dev, forces, nxt, snap = step_batch(world, st, act, bi)
             idx = _action_index(world, st.device)
         ctx.world = world
         ctx.identity = _identity_action(world, world.getNumDofs())
@@ -202,6 +234,7 @@ class TimestepLayer(torch.autograd.Function):
         # produced this snapshot, even if the world changes in between
         ctx.dev = dev
         ctx.squeeze = squeeze
+        ctx.body_inertia = bi
         ctx.save_for_backward(st, forces, snap, idx)
         if squeeze:
             # World::step side effects on the single world
@@ -225,10 +258,15 @@ class TimestepLayer(torch.autograd.Function):
             gf = torch.empty_like(forces)
             stream = torch.cuda.current_stream(st.device).cuda_stream
             gm = None
-            if ctx.use_mass and ctx.mass_shape[0] > 0:
+            bi = ctx.body_inertia
+            if ctx.per_world and ctx.mass_shape[1] > 0:
+                gm = mass_gradient(dev, ctx.mass_sel, st, forces, snap, g, gs, gf, stream, bi).to(ctx.mass_device)
+            elif ctx.use_mass and not ctx.per_world and ctx.mass_shape[0] > 0:
                 gm = mass_gradient(dev, ctx.mass_sel, st, forces, snap, g, gs, gf, stream).sum(0).to(ctx.mass_device)
-            else:
+            elif bi is None:
                 dev.backward(st, forces, snap, g, gs, gf, stream)
+            else:
+                dev.backward(st, forces, snap, g, gs, gf, stream, bi)
             ga = gf if idx.shape[0] == gf.shape[1] and ctx.identity else gf.index_select(1, idx)
         od = ctx.out_device
         if ctx.use_mass and gm is None:
