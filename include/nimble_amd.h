@@ -338,6 +338,83 @@ int nimble_constraint_force_jacobians_pw(nimble_world_t world, int32_t batch, co
                                          double* workspace, const double* body_inertia,
                                          void* stream);
 
+/*
+ * External body wrenches.  Each `_ext` entry point is its `_pw` sibling above
+ * with two more inputs:
+ *   body_wrench [batch][num_bodies][6]  device, read only
+ *   wrench_frame                        NIMBLE_WRENCH_WORLD or NIMBLE_WRENCH_BODY
+ * six doubles per body of every world, bodies in the order of
+ * nimble_world_desc and body_inertia (the massless frames of compound-joint
+ * chains included), each [torque xyz, force xyz] -- the reference's spatial
+ * order.  The frame flag holds for the whole call:
+ *   NIMBLE_WRENCH_WORLD  world axes, moment about the world origin: the
+ *     worldWrench of DifferentiableExternalForce::computeTau
+ *     (dart/neural/DifferentiableExternalForce.cpp:58); constant in q.
+ *   NIMBLE_WRENCH_BODY   body axes, moment about the body frame's origin:
+ *     BodyNode::mFext as setExtWrench / addExtForce / addExtTorque store it
+ *     (dart/dynamics/BodyNode.cpp:1532-1612); it moves with the body, the
+ *     world wrench is dAdInvT(T_world_body, F).
+ * The step adds tau_ext = sum_b J_b^T W_b to the generalized forces through
+ * the bias force, as the reference does (BodyNode.cpp:2079, mBiasForce =
+ * -dad(V, I V) - mFext - mFgravity; inverse dynamics :2010), so the
+ * unconstrained velocity, the LCP, the snapshot's dynamics cache and every
+ * derivative see it.  The wrench is an input of one step: nothing is stored
+ * in the world (the reference clears mFext after the step,
+ * dart/simulation/World.cpp:300).  A forward and every backward / Jacobian
+ * call on its snapshot must be given the same body_inertia, body_wrench and
+ * wrench_frame.  body_inertia NULL: the model's values.  body_wrench NULL:
+ * the call is the `_pw` sibling's.  Nothing is validated on the device (a NaN
+ * wrench gives NaN).
+ *
+ * Derivatives (DifferentiableExternalForce.cpp: getJacobianOfTauWrt(POSITION)
+ * :85, getJacobianOfTauWrtWorldWrench :169): grad_state's position part gains
+ * +dt (d tau_ext/dq)^T (w - nu), and
+ *   grad_wrench [batch][num_bodies][6]          (nimble_backward_ext; NULL to skip)
+ *   wrench_jacobian [batch][2n][num_bodies][6]  (nimble_jacobians_ext; NULL to skip)
+ * hold the gradient of the loss (of next-state row r) with respect to
+ * body_wrench, in the frame of the input: dt times the world twist of body b
+ * under w - nu, for NIMBLE_WRENCH_BODY taken to body coordinates.  The bound
+ * clipping of grad_forces never applies to them.  The mass, inertia and
+ * constraint-force modes take the wrench as input and have no wrench output.
+ */
+#define NIMBLE_WRENCH_WORLD 0
+#define NIMBLE_WRENCH_BODY 1
+
+int nimble_forward_ext(nimble_world_t world, int32_t batch, const double* state,
+                       const double* forces, double* lcp_cache, double* next_state,
+                       double* snapshot, const double* body_inertia,
+                       const double* body_wrench, int32_t wrench_frame, void* stream);
+int nimble_backward_ext(nimble_world_t world, int32_t batch, const double* state,
+                        const double* forces, double* snapshot,
+                        const double* grad_next_state, double* grad_state,
+                        double* grad_forces, const double* body_inertia,
+                        const double* body_wrench, int32_t wrench_frame,
+                        double* grad_wrench, void* stream);
+int nimble_backward_masses_ext(nimble_world_t world, int32_t batch, const double* state,
+                               const double* forces, double* snapshot,
+                               const double* grad_next_state, double* grad_state,
+                               double* grad_forces, double* grad_masses,
+                               const double* body_inertia, const double* body_wrench,
+                               int32_t wrench_frame, void* stream);
+int nimble_backward_inertia_ext(nimble_world_t world, int32_t batch, const double* state,
+                                const double* forces, double* snapshot,
+                                const double* grad_next_state, double* grad_state,
+                                double* grad_forces, double* grad_inertia,
+                                const double* body_inertia, const double* body_wrench,
+                                int32_t wrench_frame, void* stream);
+int nimble_jacobians_ext(nimble_world_t world, int32_t batch, const double* state,
+                         const double* forces, const double* snapshot,
+                         double* state_jacobian, double* force_jacobian,
+                         double* workspace, const double* body_inertia,
+                         const double* body_wrench, int32_t wrench_frame,
+                         double* wrench_jacobian, void* stream);
+int nimble_constraint_force_jacobians_ext(nimble_world_t world, int32_t batch, const double* state,
+                                          const double* forces, const double* snapshot,
+                                          double* dfc_dstate, double* dfc_dforces,
+                                          double* workspace, const double* body_inertia,
+                                          const double* body_wrench, int32_t wrench_frame,
+                                          void* stream);
+
 /* Last error message (thread-local). */
 const char* nimble_last_error(void);
 

@@ -14,6 +14,41 @@ LIB_PATH = os.environ.get("NIMBLE_AMD_LIB") or os.path.join(_HERE, "libnimble_am
 _lib = None
 
 
+# wrench_frame of the `_ext` entry points (include/nimble_amd.h)
+WRENCH_WORLD, WRENCH_BODY = 0, 1
+WRENCH_FRAMES = {"world": WRENCH_WORLD, "body": WRENCH_BODY}
+
+
+def wrench_frame_flag(frame) -> int:
+    """"world" / "body" (or the header's 0 / 1) -> NIMBLE_WRENCH_*."""
+    if isinstance(frame, str):
+        if frame not in WRENCH_FRAMES:
+            raise ValueError(f"wrench_frame {frame!r}: expected 'world' or 'body'")
+        return WRENCH_FRAMES[frame]
+    if isinstance(frame, bool) or not isinstance(frame, int) or frame not in (WRENCH_WORLD, WRENCH_BODY):
+        raise ValueError(f"wrench_frame {frame!r}: expected 'world' or 'body'")
+    return int(frame)
+
+
+def _ext_prototypes():
+    """argtypes of the six entry points with external body wrenches: the
+    `_pw` sibling's buffers (body_inertia the last of them), then body_wrench,
+    wrench_frame, the wrench-gradient output where there is one, the stream."""
+    v, i = C.c_void_p, C.c_int32
+    head = [v, i]
+    return {
+        "nimble_forward_ext": head + [v] * 6 + [v, i, v],
+        "nimble_backward_ext": head + [v] * 7 + [v, i, v, v],
+        "nimble_backward_masses_ext": head + [v] * 8 + [v, i, v],
+        "nimble_backward_inertia_ext": head + [v] * 8 + [v, i, v],
+        "nimble_jacobians_ext": head + [v] * 7 + [v, i, v, v],
+        "nimble_constraint_force_jacobians_ext": head + [v] * 7 + [v, i, v],
+    }
+
+
+EXT_PROTOTYPES = _ext_prototypes()
+
+
 class NativeLibraryMissing(ImportError):
     pass
 
@@ -57,6 +92,10 @@ def lib():
                               ("nimble_constraint_force_jacobians_pw", 7)):
             f = getattr(L, name)
             f.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * buffers + [C.c_void_p]
+            f.restype = C.c_int
+        for name, argtypes in EXT_PROTOTYPES.items():
+            f = getattr(L, name)
+            f.argtypes = argtypes
             f.restype = C.c_int
         L.nimble_num_collision_pairs.restype = C.c_int32
         _lib = L
@@ -199,6 +238,31 @@ class DeviceWorld:
         if not t.is_contiguous():
             raise ValueError("nimblephysics_amd buffers must be contiguous")
 
+    def _wrench(self, B, body_wrench, wrench_frame, grad_wrench=None, rows=None):
+        """Checks the optional external body wrenches (include/nimble_amd.h
+        body_wrench: [B, num_bodies, 6] float64, [torque xyz, force xyz] per
+        body in device-model order) and the output for their gradient;
+        returns the frame flag.  None: no wrench."""
+        flag = wrench_frame_flag(wrench_frame)
+        t = body_wrench
+        if t is None:
+            if grad_wrench is not None:
+                raise ValueError("grad_wrench given without body_wrench")
+            return flag
+        if tuple(t.shape) != (B, self.nb, 6):
+            raise ValueError(f"body_wrench shape {tuple(t.shape)} != ({B}, {self.nb}, 6)")
+        if str(t.dtype) != "torch.float64":
+            raise TypeError("body_wrench must be float64 (the reference's s_t); got " + str(t.dtype))
+        if not t.is_contiguous():
+            raise ValueError("nimblephysics_amd buffers must be contiguous")
+        if grad_wrench is not None:
+            want = (B, self.nb, 6) if rows is None else (B, rows, self.nb, 6)
+            if tuple(grad_wrench.shape) != want or not grad_wrench.is_contiguous():
+                raise ValueError(f"grad_wrench shape {tuple(grad_wrench.shape)} != {want}")
+            if str(grad_wrench.dtype) != "torch.float64":
+                raise TypeError("grad_wrench must be float64; got " + str(grad_wrench.dtype))
+        return flag
+
     def status(self, snapshot):
         """Status bits per world ([B] int32, device) of the forward that wrote
         `snapshot`; zeros for models without collision pairs."""
@@ -207,10 +271,18 @@ class DeviceWorld:
             return torch.zeros(snapshot.shape[0], dtype=torch.int32, device=snapshot.device)
         return snapshot[:, SN_STATUS].to(torch.int32)
 
-    def forward(self, state, forces, lcp_cache, next_state, snapshot, stream_ptr: int, body_inertia=None):
+    def forward(self, state, forces, lcp_cache, next_state, snapshot, stream_ptr: int, body_inertia=None,
+                body_wrench=None, wrench_frame="world"):
         """nimble_forward; with `body_inertia` [B, num_bodies, 10] every world
         steps with its own body parameters (nimble_forward_pw), and the
-        backward / Jacobian calls on its snapshot take the same tensor."""
+        backward / Jacobian calls on its snapshot take the same tensor.  With
+        `body_wrench` [B, num_bodies, 6] the bodies are pushed by those
+        wrenches, given in `wrench_frame` (nimble_forward_ext); the other
+        calls on the snapshot take them too.  (Without: nothing but this test
+        is added to the path, which benchmarks time from the host side.)"""
+        if body_wrench is not None:
+            return self._ext("forward", state, forces, (lcp_cache, next_state, snapshot), stream_ptr, body_inertia,
+                             body_wrench, wrench_frame)
         B = state.shape[0]
         self._inertia(B, body_inertia)
         _require_device(state, forces, lcp_cache, next_state, snapshot, body_inertia)
@@ -224,7 +296,13 @@ class DeviceWorld:
                                     _ptr(snapshot), C.c_void_p(stream_ptr)))
 
     def backward(self, state, forces, snapshot, grad_next, grad_state, grad_forces, stream_ptr: int,
-                 body_inertia=None):
+                 body_inertia=None, body_wrench=None, wrench_frame="world", grad_wrench=None):
+        """nimble_backward; `grad_wrench` [B, num_bodies, 6] (with
+        `body_wrench`) receives the gradient with respect to the wrenches, in
+        their frame (nimble_backward_ext)."""
+        if body_wrench is not None or grad_wrench is not None:
+            return self._ext("backward", state, forces, (snapshot, grad_next, grad_state, grad_forces), stream_ptr,
+                             body_inertia, body_wrench, wrench_frame, grad_wrench)
         B = state.shape[0]
         self._inertia(B, body_inertia)
         _require_device(state, forces, snapshot, grad_next, grad_state, grad_forces, body_inertia)
@@ -241,8 +319,14 @@ class DeviceWorld:
                                      _ptr(grad_state), _ptr(grad_forces), C.c_void_p(stream_ptr)))
 
     def backward_masses(self, state, forces, snapshot, grad_next, grad_state, grad_forces, grad_masses,
-                        stream_ptr: int, body_inertia=None):
+                        stream_ptr: int, body_inertia=None, body_wrench=None, wrench_frame="world"):
         """backward() plus dL/d(body masses) [B, num_bodies] (nimble_backward_masses)."""
+        if body_wrench is not None:
+            if tuple(grad_masses.shape) != (state.shape[0], self.nb) or not grad_masses.is_contiguous():
+                raise ValueError(f"grad_masses shape {tuple(grad_masses.shape)} != ({state.shape[0]}, {self.nb})")
+            return self._ext("backward_masses", state, forces, (snapshot, grad_next, grad_state, grad_forces,
+                                                                grad_masses), stream_ptr, body_inertia, body_wrench,
+                             wrench_frame)
         B = state.shape[0]
         self._inertia(B, body_inertia)
         _require_device(state, forces, snapshot, grad_next, grad_state, grad_forces, grad_masses, body_inertia)
@@ -262,11 +346,17 @@ class DeviceWorld:
                                             C.c_void_p(stream_ptr)))
 
     def backward_inertia(self, state, forces, snapshot, grad_next, grad_state, grad_forces, grad_inertia,
-                         stream_ptr: int, body_inertia=None):
+                         stream_ptr: int, body_inertia=None, body_wrench=None, wrench_frame="world"):
         """backward() plus dL/d(body inertia parameters) [B, num_bodies, 10] in
         INERTIA_FULL order (mass, COM xyz, Ixx Iyy Izz Ixy Ixz Iyz;
         nimble_backward_inertia): with `body_inertia`, the gradient with
         respect to that array."""
+        if body_wrench is not None:
+            if tuple(grad_inertia.shape) != (state.shape[0], self.nb, 10) or not grad_inertia.is_contiguous():
+                raise ValueError(f"grad_inertia shape {tuple(grad_inertia.shape)} != ({state.shape[0]}, {self.nb}, 10)")
+            return self._ext("backward_inertia", state, forces, (snapshot, grad_next, grad_state, grad_forces,
+                                                                 grad_inertia), stream_ptr, body_inertia, body_wrench,
+                             wrench_frame)
         B = state.shape[0]
         self._inertia(B, body_inertia)
         _require_device(state, forces, snapshot, grad_next, grad_state, grad_forces, grad_inertia, body_inertia)
@@ -285,10 +375,73 @@ class DeviceWorld:
                                              _ptr(grad_state), _ptr(grad_forces), _ptr(grad_inertia),
                                              C.c_void_p(stream_ptr)))
 
-    def jacobians(self, state, forces, snapshot, stream_ptr: int, body_inertia=None):
-        """(d next_state / d state [B, 2n, 2n], d next_state / d forces
-        [B, 2n, n]) of the forward that wrote `snapshot` (nimble_jacobians)."""
+    def _ext(self, mode, state, forces, buffers, stream_ptr, body_inertia, body_wrench, wrench_frame,
+             grad_wrench=None, wrench_jacobian=False):
+        """The calls with external body wrenches (the `_ext` entry points):
+        `mode` names the wrapper, `buffers` its tensors after state and forces
+        in the entry point's order.  The Jacobian modes allocate their
+        outputs as the wrappers without wrenches do."""
         import torch
+        B = state.shape[0]
+        n = self.n
+        self._inertia(B, body_inertia)
+        frame = self._wrench(B, body_wrench, wrench_frame, grad_wrench)
+        _require_device(state, forces, *buffers, body_inertia, body_wrench, grad_wrench)
+        self._on_my_device(state, forces, *buffers, body_inertia, body_wrench, grad_wrench)
+        L = lib()
+        stream = C.c_void_p(stream_ptr)
+        tail = (_ptr(body_inertia), _ptr(body_wrench), frame)
+        if mode == "forward":
+            lcp_cache, next_state, snapshot = buffers
+            self._shapes(B, state, forces, snapshot, lcp_cache)
+            _check(L.nimble_forward_ext(self.h, B, _ptr(state), _ptr(forces), _ptr(lcp_cache), _ptr(next_state),
+                                        _ptr(snapshot), *tail, stream))
+            return None
+        if mode in ("jacobians", "constraint_force_jacobians"):
+            snapshot, = buffers
+            self._shapes(B, state, forces, snapshot)
+            wsd = int(L.nimble_jacobian_workspace_doubles(self.h, B))
+            ws = torch.empty(wsd, dtype=torch.float64, device=state.device) if wsd > 0 else None
+            if mode == "jacobians":
+                J = torch.empty((B, 2 * n, 2 * n), dtype=torch.float64, device=state.device)
+                F = torch.empty((B, 2 * n, n), dtype=torch.float64, device=state.device)
+                W = torch.empty((B, 2 * n, self.nb, 6), dtype=torch.float64, device=state.device) \
+                    if wrench_jacobian else None
+                _check(L.nimble_jacobians_ext(self.h, B, _ptr(state), _ptr(forces), _ptr(snapshot), _ptr(J), _ptr(F),
+                                              _ptr(ws), *tail, _ptr(W), stream))
+                return (J, F, W) if wrench_jacobian else (J, F)
+            Js = torch.empty((B, MAX_LCP, 2 * n), dtype=torch.float64, device=state.device)
+            Jf = torch.empty((B, MAX_LCP, n), dtype=torch.float64, device=state.device)
+            _check(L.nimble_constraint_force_jacobians_ext(self.h, B, _ptr(state), _ptr(forces), _ptr(snapshot),
+                                                           _ptr(Js), _ptr(Jf), _ptr(ws), *tail, stream))
+            return Js, Jf
+        snapshot, grad_next, grad_state, grad_forces = buffers[:4]
+        self._shapes(B, state, forces, snapshot)
+        self._shapes(B, grad_next, grad_forces)
+        self._shapes(B, grad_state)
+        head = (self.h, B, _ptr(state), _ptr(forces), _ptr(snapshot), _ptr(grad_next), _ptr(grad_state),
+                _ptr(grad_forces))
+        if mode == "backward":
+            _check(L.nimble_backward_ext(*head, *tail, _ptr(grad_wrench), stream))
+        elif mode == "backward_masses":
+            _check(L.nimble_backward_masses_ext(*head, _ptr(buffers[4]), *tail, stream))
+        else:
+            _check(L.nimble_backward_inertia_ext(*head, _ptr(buffers[4]), *tail, stream))
+        return None
+
+    def jacobians(self, state, forces, snapshot, stream_ptr: int, body_inertia=None, body_wrench=None,
+                  wrench_frame="world", wrench_jacobian=False):
+        """(d next_state / d state [B, 2n, 2n], d next_state / d forces
+        [B, 2n, n]) of the forward that wrote `snapshot` (nimble_jacobians).
+        `wrench_jacobian=True` (with `body_wrench`): a third result,
+        d next_state / d body_wrench [B, 2n, num_bodies, 6]
+        (nimble_jacobians_ext)."""
+        import torch
+        if wrench_jacobian and body_wrench is None:
+            raise ValueError("wrench_jacobian needs body_wrench")
+        if body_wrench is not None:
+            return self._ext("jacobians", state, forces, (snapshot,), stream_ptr, body_inertia, body_wrench,
+                             wrench_frame, wrench_jacobian=wrench_jacobian)
         B = state.shape[0]
         self._inertia(B, body_inertia)
         _require_device(state, forces, snapshot, body_inertia)
@@ -307,11 +460,15 @@ class DeviceWorld:
                                       _ptr(ws), C.c_void_p(stream_ptr)))
         return J, F
 
-    def constraint_force_jacobians(self, state, forces, snapshot, stream_ptr: int, body_inertia=None):
+    def constraint_force_jacobians(self, state, forces, snapshot, stream_ptr: int, body_inertia=None,
+                                   body_wrench=None, wrench_frame="world"):
         """(d f_c / d state [B, MAX_LCP, 2n], d f_c / d forces [B, MAX_LCP, n])
         of the forward that wrote `snapshot` (nimble_constraint_force_jacobians;
         rows past each world's clamping count are zero)."""
         import torch
+        if body_wrench is not None:
+            return self._ext("constraint_force_jacobians", state, forces, (snapshot,), stream_ptr, body_inertia,
+                             body_wrench, wrench_frame)
         B = state.shape[0]
         self._inertia(B, body_inertia)
         _require_device(state, forces, snapshot, body_inertia)

@@ -46,6 +46,18 @@ struct nimble_world {
   int cacheDoubles = NIMBLE_MAX_LCP + 1;
   hipFunction_t dummy = nullptr;
   double* meshDev = nullptr;  // ModelDev::meshVerts
+  // the model's own body parameters as one [nb][10] block of body_inertia
+  // (the `_ext` kernels read every world's parameters from such blocks; with
+  // the caller's body_inertia NULL they get this one, batch stride 0)
+  double* inertiaDev = nullptr;
+};
+
+// body_wrench of an `_ext` call (nullptr: none), its frame flag, and the
+// wrench-gradient output of the backward / Jacobian modes that have one
+struct ExtArgs {
+  const double* wrench = nullptr;
+  int frame = NIMBLE_WRENCH_WORLD;
+  double* gradWrench = nullptr;
 };
 
 extern "C" __global__ void nimble_forward_kernel(const ModelDev*, Layout, const double*, const double*, double*,
@@ -73,6 +85,24 @@ extern "C" __global__ void nimble_backward_pw_kernel(const ModelDev*, int, const
 extern "C" __global__ void nimble_backward_wide_pw_kernel(const ModelDev*, int, const double*, const double*,
                                                           double*, int, const double*, double*, double*, int, double*,
                                                           int, double*, int, int, int, const double*);
+
+// the instances that take external body wrenches (timestep_ext.hip): per-world
+// parameters with their batch stride, body_wrench [batch][num_bodies][6], the
+// frame flag, and (backward) grad_wrench
+extern "C" __global__ void nimble_forward_ext_kernel(const ModelDev*, Layout, const double*, const double*, double*,
+                                                     double*, double*, int, int, int, int, const double*, int,
+                                                     const double*, int);
+extern "C" __global__ void nimble_forward_mesh_ext_kernel(const ModelDev*, Layout, const double*, const double*,
+                                                          double*, double*, double*, int, int, int, int,
+                                                          const double*, int, const double*, int);
+extern "C" __global__ void nimble_backward_ext_kernel(const ModelDev*, int, const double*, const double*,
+                                                      double*, int, const double*, double*, double*, int, double*, int,
+                                                      double*, int, int, int, const double*, int, const double*, int,
+                                                      double*);
+extern "C" __global__ void nimble_backward_wide_ext_kernel(const ModelDev*, int, const double*, const double*,
+                                                           double*, int, const double*, double*, double*, int, double*,
+                                                           int, double*, int, int, int, const double*, int,
+                                                           const double*, int, double*);
 
 static void isoInverse(const double* T, double* O) {
   // [R|p]^-1 = [R^T | -R^T p]
@@ -462,6 +492,27 @@ int nimble_world_create(const nimble_world_desc* d, nimble_world_t* out) {
     delete w;
     return fail(NIMBLE_ERR_HIP, std::string("hipMemcpy: ") + hipGetErrorString(e));
   }
+  {
+    // INERTIA_FULL rows of the model's values (Ic was filled from the six
+    // moments by placement, so these are the description's numbers)
+    std::vector<double> bi((size_t)m.nb * 10);
+    for (int b = 0; b < m.nb; b++) {
+      double* r = bi.data() + 10 * b;
+      r[0] = m.mass[b];
+      for (int i = 0; i < 3; i++) r[1 + i] = m.com[b][i];
+      r[4] = m.Ic[b][0]; r[5] = m.Ic[b][4]; r[6] = m.Ic[b][8];
+      r[7] = m.Ic[b][1]; r[8] = m.Ic[b][2]; r[9] = m.Ic[b][5];
+    }
+    e = hipMalloc(&w->inertiaDev, bi.size() * sizeof(double));
+    if (e == hipSuccess) e = hipMemcpy(w->inertiaDev, bi.data(), bi.size() * sizeof(double), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+      if (w->inertiaDev) (void)hipFree(w->inertiaDev);
+      (void)hipFree(w->dev);
+      if (w->meshDev) (void)hipFree(w->meshDev);
+      delete w;
+      return fail(NIMBLE_ERR_HIP, std::string("body parameters: ") + hipGetErrorString(e));
+    }
+  }
   *out = w;
   return NIMBLE_OK;
 }
@@ -469,6 +520,7 @@ int nimble_world_create(const nimble_world_desc* d, nimble_world_t* out) {
 int nimble_world_destroy(nimble_world_t w) {
   if (!w) return NIMBLE_OK;
   if (w->dev) (void)hipFree(w->dev);
+  if (w->inertiaDev) (void)hipFree(w->inertiaDev);
   if (w->meshDev) (void)hipFree(w->meshDev);
   delete w;
   return NIMBLE_OK;
@@ -497,8 +549,32 @@ int nimble_forward(nimble_world_t w, int32_t batch, const double* state, const d
   return nimble_forward_pw(w, batch, state, forces, lcp_cache, next_state, snapshot, nullptr, stream);
 }
 
+static int forwardImpl(nimble_world_t w, int32_t batch, const double* state, const double* forces, double* lcp_cache,
+                       double* next_state, double* snapshot, const double* body_inertia, const ExtArgs& ext,
+                       void* stream);
+
 int nimble_forward_pw(nimble_world_t w, int32_t batch, const double* state, const double* forces, double* lcp_cache,
                       double* next_state, double* snapshot, const double* body_inertia, void* stream) {
+  return forwardImpl(w, batch, state, forces, lcp_cache, next_state, snapshot, body_inertia, ExtArgs{}, stream);
+}
+
+static bool badFrame(int32_t f) { return f != NIMBLE_WRENCH_WORLD && f != NIMBLE_WRENCH_BODY; }
+
+int nimble_forward_ext(nimble_world_t w, int32_t batch, const double* state, const double* forces, double* lcp_cache,
+                       double* next_state, double* snapshot, const double* body_inertia, const double* body_wrench,
+                       int32_t wrench_frame, void* stream) {
+  if (!body_wrench)
+    return nimble_forward_pw(w, batch, state, forces, lcp_cache, next_state, snapshot, body_inertia, stream);
+  if (badFrame(wrench_frame)) return fail(NIMBLE_ERR_INVALID, "bad wrench frame");
+  ExtArgs ext;
+  ext.wrench = body_wrench;
+  ext.frame = wrench_frame;
+  return forwardImpl(w, batch, state, forces, lcp_cache, next_state, snapshot, body_inertia, ext, stream);
+}
+
+static int forwardImpl(nimble_world_t w, int32_t batch, const double* state, const double* forces, double* lcp_cache,
+                       double* next_state, double* snapshot, const double* body_inertia, const ExtArgs& ext,
+                       void* stream) {
   if (!w || batch < 0) return fail(NIMBLE_ERR_INVALID, "bad arguments");
   if (batch == 0) return NIMBLE_OK;
   if (!state || !forces || !next_state || !snapshot || !lcp_cache) return fail(NIMBLE_ERR_INVALID, "null buffer");
@@ -528,7 +604,27 @@ int nimble_forward_pw(nimble_world_t w, int32_t batch, const double* state, cons
     // (per-world body parameters: the instances that read body_inertia; the
     // wide kernel below reloads their dynamics cache and needs no inertia)
     const double* bi = body_inertia ? body_inertia + (size_t)b0 * w->host.nb * 10 : nullptr;
-    if (bi && w->host.hasMesh)
+    if (ext.wrench) {
+      // (external body wrenches: the instances that read body_wrench; they
+      // always read per-world parameters -- the model's own block, stride 0,
+      // when none are given -- and cache a bias that holds the wrench, which
+      // the wide kernel below reloads)
+      const double* ebi = bi ? bi : w->inertiaDev;
+      const int stride = bi ? w->host.nb * 10 : 0;
+      const double* bw = ext.wrench + (size_t)b0 * w->host.nb * 6;
+      if (w->host.hasMesh)
+        hipLaunchKernelGGL(nimble_forward_mesh_ext_kernel, dim3(cnt), dim3(fwdThreads), lds, st, w->dev, w->fwd,
+                           state + b0 * 2 * n, forces + b0 * n, lcp_cache + (size_t)b0 * w->cacheDoubles,
+                           next_state + b0 * 2 * n, snapshot + (size_t)b0 * w->snapDoubles, w->snapDoubles,
+                           w->cacheDoubles, w->fwdDeferRows, wide && largestFirst ? 1 : 0, ebi, stride, bw,
+                           ext.frame);
+      else
+        hipLaunchKernelGGL(nimble_forward_ext_kernel, dim3(cnt), dim3(fwdThreads), lds, st, w->dev, w->fwd,
+                           state + b0 * 2 * n, forces + b0 * n, lcp_cache + (size_t)b0 * w->cacheDoubles,
+                           next_state + b0 * 2 * n, snapshot + (size_t)b0 * w->snapDoubles, w->snapDoubles,
+                           w->cacheDoubles, w->fwdDeferRows, wide && largestFirst ? 1 : 0, ebi, stride, bw,
+                           ext.frame);
+    } else if (bi && w->host.hasMesh)
       hipLaunchKernelGGL(nimble_forward_mesh_pw_kernel, dim3(cnt), dim3(fwdThreads), lds, st, w->dev, w->fwd,
                          state + b0 * 2 * n, forces + b0 * n, lcp_cache + (size_t)b0 * w->cacheDoubles,
                          next_state + b0 * 2 * n, snapshot + (size_t)b0 * w->snapDoubles, w->snapDoubles,
@@ -569,8 +665,23 @@ int nimble_forward_pw(nimble_world_t w, int32_t batch, const double* state, cons
 static hipError_t launchBackward(nimble_world_t w, int grid, hipStream_t st, int batch, const double* state,
                                  const double* forces, double* snapshot, const double* gradNext, double* gradState,
                                  double* gradForces, int rows, double* ws, int wsDoubles, double* gradMasses,
-                                 int fcMode, int massParams, const double* bodyInertia) {
+                                 int fcMode, int massParams, const double* bodyInertia,
+                                 const ExtArgs& ext = ExtArgs{}) {
   const size_t lds = (size_t)w->bwd.total * sizeof(double);
+  if (ext.wrench) {
+    // external body wrenches (see forwardImpl for the parameter block)
+    const double* ebi = bodyInertia ? bodyInertia : w->inertiaDev;
+    const int stride = bodyInertia ? w->host.nb * 10 : 0;
+    hipLaunchKernelGGL(nimble_backward_ext_kernel, dim3(grid), dim3(64), lds, st, w->dev, batch, state, forces,
+                       snapshot, w->snapDoubles, gradNext, gradState, gradForces, rows, ws, wsDoubles, gradMasses,
+                       fcMode, massParams, w->deferRows, ebi, stride, ext.wrench, ext.frame, ext.gradWrench);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess || w->host.numPairs == 0 || w->maxRows <= w->deferRows) return e;
+    hipLaunchKernelGGL(nimble_backward_wide_ext_kernel, dim3(grid), dim3(64), lds, st, w->dev, batch, state, forces,
+                       snapshot, w->snapDoubles, gradNext, gradState, gradForces, rows, ws, wsDoubles, gradMasses,
+                       fcMode, massParams, w->deferRows, ebi, stride, ext.wrench, ext.frame, ext.gradWrench);
+    return hipGetLastError();
+  }
   if (bodyInertia) {
     hipLaunchKernelGGL(nimble_backward_pw_kernel, dim3(grid), dim3(64), lds, st, w->dev, batch, state, forces,
                        snapshot, w->snapDoubles, gradNext, gradState, gradForces, rows, ws, wsDoubles, gradMasses,
@@ -600,16 +711,43 @@ int nimble_backward(nimble_world_t w, int32_t batch, const double* state, const 
                             stream);
 }
 
+static int backwardImpl(nimble_world_t w, int32_t batch, const double* state, const double* forces,
+                        double* snapshot, const double* grad_next_state, double* grad_state, double* grad_forces,
+                        const double* body_inertia, const ExtArgs& ext, void* stream);
+
 int nimble_backward_pw(nimble_world_t w, int32_t batch, const double* state, const double* forces,
                        double* snapshot, const double* grad_next_state, double* grad_state,
                        double* grad_forces, const double* body_inertia, void* stream) {
+  return backwardImpl(w, batch, state, forces, snapshot, grad_next_state, grad_state, grad_forces, body_inertia,
+                      ExtArgs{}, stream);
+}
+
+int nimble_backward_ext(nimble_world_t w, int32_t batch, const double* state, const double* forces,
+                        double* snapshot, const double* grad_next_state, double* grad_state,
+                        double* grad_forces, const double* body_inertia, const double* body_wrench,
+                        int32_t wrench_frame, double* grad_wrench, void* stream) {
+  if (!body_wrench)
+    return nimble_backward_pw(w, batch, state, forces, snapshot, grad_next_state, grad_state, grad_forces,
+                              body_inertia, stream);
+  if (badFrame(wrench_frame)) return fail(NIMBLE_ERR_INVALID, "bad wrench frame");
+  ExtArgs ext;
+  ext.wrench = body_wrench;
+  ext.frame = wrench_frame;
+  ext.gradWrench = grad_wrench;
+  return backwardImpl(w, batch, state, forces, snapshot, grad_next_state, grad_state, grad_forces, body_inertia, ext,
+                      stream);
+}
+
+static int backwardImpl(nimble_world_t w, int32_t batch, const double* state, const double* forces,
+                        double* snapshot, const double* grad_next_state, double* grad_state, double* grad_forces,
+                        const double* body_inertia, const ExtArgs& ext, void* stream) {
   if (!w || batch < 0) return fail(NIMBLE_ERR_INVALID, "bad arguments");
   if (batch == 0) return NIMBLE_OK;
   if (!state || !forces || !grad_next_state || !grad_state || !grad_forces || !snapshot)
     return fail(NIMBLE_ERR_INVALID, "null buffer");
   hipStream_t st = (hipStream_t)stream;
   HIP_TRY(launchBackward(w, gridFor(batch), st, batch, state, forces, snapshot, grad_next_state, grad_state,
-                        grad_forces, 1, nullptr, 0, nullptr, 0, 1, body_inertia));
+                        grad_forces, 1, nullptr, 0, nullptr, 0, 1, body_inertia, ext));
   return NIMBLE_OK;
 }
 
@@ -620,16 +758,44 @@ int nimble_backward_masses(nimble_world_t w, int32_t batch, const double* state,
                                    grad_masses, nullptr, stream);
 }
 
+static int backwardMassesImpl(nimble_world_t w, int32_t batch, const double* state, const double* forces,
+                              double* snapshot, const double* grad_next_state, double* grad_state,
+                              double* grad_forces, double* grad_masses, const double* body_inertia,
+                              const ExtArgs& ext, void* stream);
+
 int nimble_backward_masses_pw(nimble_world_t w, int32_t batch, const double* state, const double* forces,
                               double* snapshot, const double* grad_next_state, double* grad_state,
                               double* grad_forces, double* grad_masses, const double* body_inertia, void* stream) {
+  return backwardMassesImpl(w, batch, state, forces, snapshot, grad_next_state, grad_state, grad_forces, grad_masses,
+                            body_inertia, ExtArgs{}, stream);
+}
+
+int nimble_backward_masses_ext(nimble_world_t w, int32_t batch, const double* state, const double* forces,
+                               double* snapshot, const double* grad_next_state, double* grad_state,
+                               double* grad_forces, double* grad_masses, const double* body_inertia,
+                               const double* body_wrench, int32_t wrench_frame, void* stream) {
+  if (!body_wrench)
+    return nimble_backward_masses_pw(w, batch, state, forces, snapshot, grad_next_state, grad_state, grad_forces,
+                                     grad_masses, body_inertia, stream);
+  if (badFrame(wrench_frame)) return fail(NIMBLE_ERR_INVALID, "bad wrench frame");
+  ExtArgs ext;
+  ext.wrench = body_wrench;
+  ext.frame = wrench_frame;
+  return backwardMassesImpl(w, batch, state, forces, snapshot, grad_next_state, grad_state, grad_forces, grad_masses,
+                            body_inertia, ext, stream);
+}
+
+static int backwardMassesImpl(nimble_world_t w, int32_t batch, const double* state, const double* forces,
+                              double* snapshot, const double* grad_next_state, double* grad_state,
+                              double* grad_forces, double* grad_masses, const double* body_inertia,
+                              const ExtArgs& ext, void* stream) {
   if (!w || batch < 0) return fail(NIMBLE_ERR_INVALID, "bad arguments");
   if (batch == 0) return NIMBLE_OK;
   if (!state || !forces || !grad_next_state || !grad_state || !grad_forces || !snapshot || !grad_masses)
     return fail(NIMBLE_ERR_INVALID, "null buffer");
   hipStream_t st = (hipStream_t)stream;
   HIP_TRY(launchBackward(w, gridFor(batch), st, batch, state, forces, snapshot, grad_next_state, grad_state,
-                        grad_forces, 1, nullptr, 0, grad_masses, 0, 1, body_inertia));
+                        grad_forces, 1, nullptr, 0, grad_masses, 0, 1, body_inertia, ext));
   return NIMBLE_OK;
 }
 
@@ -640,16 +806,44 @@ int nimble_backward_inertia(nimble_world_t w, int32_t batch, const double* state
                                     grad_inertia, nullptr, stream);
 }
 
+static int backwardInertiaImpl(nimble_world_t w, int32_t batch, const double* state, const double* forces,
+                               double* snapshot, const double* grad_next_state, double* grad_state,
+                               double* grad_forces, double* grad_inertia, const double* body_inertia,
+                               const ExtArgs& ext, void* stream);
+
 int nimble_backward_inertia_pw(nimble_world_t w, int32_t batch, const double* state, const double* forces,
                                double* snapshot, const double* grad_next_state, double* grad_state,
                                double* grad_forces, double* grad_inertia, const double* body_inertia, void* stream) {
+  return backwardInertiaImpl(w, batch, state, forces, snapshot, grad_next_state, grad_state, grad_forces,
+                             grad_inertia, body_inertia, ExtArgs{}, stream);
+}
+
+int nimble_backward_inertia_ext(nimble_world_t w, int32_t batch, const double* state, const double* forces,
+                                double* snapshot, const double* grad_next_state, double* grad_state,
+                                double* grad_forces, double* grad_inertia, const double* body_inertia,
+                                const double* body_wrench, int32_t wrench_frame, void* stream) {
+  if (!body_wrench)
+    return nimble_backward_inertia_pw(w, batch, state, forces, snapshot, grad_next_state, grad_state, grad_forces,
+                                      grad_inertia, body_inertia, stream);
+  if (badFrame(wrench_frame)) return fail(NIMBLE_ERR_INVALID, "bad wrench frame");
+  ExtArgs ext;
+  ext.wrench = body_wrench;
+  ext.frame = wrench_frame;
+  return backwardInertiaImpl(w, batch, state, forces, snapshot, grad_next_state, grad_state, grad_forces,
+                             grad_inertia, body_inertia, ext, stream);
+}
+
+static int backwardInertiaImpl(nimble_world_t w, int32_t batch, const double* state, const double* forces,
+                               double* snapshot, const double* grad_next_state, double* grad_state,
+                               double* grad_forces, double* grad_inertia, const double* body_inertia,
+                               const ExtArgs& ext, void* stream) {
   if (!w || batch < 0) return fail(NIMBLE_ERR_INVALID, "bad arguments");
   if (batch == 0) return NIMBLE_OK;
   if (!state || !forces || !grad_next_state || !grad_state || !grad_forces || !snapshot || !grad_inertia)
     return fail(NIMBLE_ERR_INVALID, "null buffer");
   hipStream_t st = (hipStream_t)stream;
   HIP_TRY(launchBackward(w, gridFor(batch), st, batch, state, forces, snapshot, grad_next_state, grad_state,
-                        grad_forces, 1, nullptr, 0, grad_inertia, 0, 10, body_inertia));
+                        grad_forces, 1, nullptr, 0, grad_inertia, 0, 10, body_inertia, ext));
   return NIMBLE_OK;
 }
 
@@ -675,9 +869,36 @@ int nimble_jacobians(nimble_world_t w, int32_t batch, const double* state, const
                              stream);
 }
 
+static int jacobiansImpl(nimble_world_t w, int32_t batch, const double* state, const double* forces,
+                         const double* snapshot, double* state_jacobian, double* force_jacobian, double* workspace,
+                         const double* body_inertia, const ExtArgs& ext, void* stream);
+
 int nimble_jacobians_pw(nimble_world_t w, int32_t batch, const double* state, const double* forces,
                         const double* snapshot, double* state_jacobian, double* force_jacobian, double* workspace,
                         const double* body_inertia, void* stream) {
+  return jacobiansImpl(w, batch, state, forces, snapshot, state_jacobian, force_jacobian, workspace, body_inertia,
+                       ExtArgs{}, stream);
+}
+
+int nimble_jacobians_ext(nimble_world_t w, int32_t batch, const double* state, const double* forces,
+                         const double* snapshot, double* state_jacobian, double* force_jacobian, double* workspace,
+                         const double* body_inertia, const double* body_wrench, int32_t wrench_frame,
+                         double* wrench_jacobian, void* stream) {
+  if (!body_wrench)
+    return nimble_jacobians_pw(w, batch, state, forces, snapshot, state_jacobian, force_jacobian, workspace,
+                               body_inertia, stream);
+  if (badFrame(wrench_frame)) return fail(NIMBLE_ERR_INVALID, "bad wrench frame");
+  ExtArgs ext;
+  ext.wrench = body_wrench;
+  ext.frame = wrench_frame;
+  ext.gradWrench = wrench_jacobian;
+  return jacobiansImpl(w, batch, state, forces, snapshot, state_jacobian, force_jacobian, workspace, body_inertia,
+                       ext, stream);
+}
+
+static int jacobiansImpl(nimble_world_t w, int32_t batch, const double* state, const double* forces,
+                         const double* snapshot, double* state_jacobian, double* force_jacobian, double* workspace,
+                         const double* body_inertia, const ExtArgs& ext, void* stream) {
   if (!w || batch < 0) return fail(NIMBLE_ERR_INVALID, "bad arguments");
   if (batch == 0 || w->host.n == 0) return NIMBLE_OK;
   if (!state || !forces || !snapshot || !state_jacobian || !force_jacobian)
@@ -690,7 +911,7 @@ int nimble_jacobians_pw(nimble_world_t w, int32_t batch, const double* state, co
   hipStream_t st = (hipStream_t)stream;
   HIP_TRY(launchBackward(w, grid, st, batch, state, forces, const_cast<double*>(snapshot), nullptr, state_jacobian,
                         force_jacobian, rows, w->jacWsDoubles > 0 ? workspace : nullptr, w->jacWsDoubles, nullptr, 0,
-                        1, body_inertia));
+                        1, body_inertia, ext));
   return NIMBLE_OK;
 }
 
@@ -701,9 +922,35 @@ int nimble_constraint_force_jacobians(nimble_world_t w, int32_t batch, const dou
                                               nullptr, stream);
 }
 
+static int fcJacobiansImpl(nimble_world_t w, int32_t batch, const double* state, const double* forces,
+                           const double* snapshot, double* dfc_dstate, double* dfc_dforces, double* workspace,
+                           const double* body_inertia, const ExtArgs& ext, void* stream);
+
 int nimble_constraint_force_jacobians_pw(nimble_world_t w, int32_t batch, const double* state, const double* forces,
                                          const double* snapshot, double* dfc_dstate, double* dfc_dforces,
                                          double* workspace, const double* body_inertia, void* stream) {
+  return fcJacobiansImpl(w, batch, state, forces, snapshot, dfc_dstate, dfc_dforces, workspace, body_inertia,
+                         ExtArgs{}, stream);
+}
+
+int nimble_constraint_force_jacobians_ext(nimble_world_t w, int32_t batch, const double* state, const double* forces,
+                                          const double* snapshot, double* dfc_dstate, double* dfc_dforces,
+                                          double* workspace, const double* body_inertia, const double* body_wrench,
+                                          int32_t wrench_frame, void* stream) {
+  if (!body_wrench)
+    return nimble_constraint_force_jacobians_pw(w, batch, state, forces, snapshot, dfc_dstate, dfc_dforces, workspace,
+                                                body_inertia, stream);
+  if (badFrame(wrench_frame)) return fail(NIMBLE_ERR_INVALID, "bad wrench frame");
+  ExtArgs ext;
+  ext.wrench = body_wrench;
+  ext.frame = wrench_frame;
+  return fcJacobiansImpl(w, batch, state, forces, snapshot, dfc_dstate, dfc_dforces, workspace, body_inertia, ext,
+                         stream);
+}
+
+static int fcJacobiansImpl(nimble_world_t w, int32_t batch, const double* state, const double* forces,
+                           const double* snapshot, double* dfc_dstate, double* dfc_dforces, double* workspace,
+                           const double* body_inertia, const ExtArgs& ext, void* stream) {
   if (!w || batch < 0) return fail(NIMBLE_ERR_INVALID, "bad arguments");
   if (batch == 0 || w->host.n == 0) return NIMBLE_OK;
   if (!state || !forces || !snapshot || !dfc_dstate || !dfc_dforces) return fail(NIMBLE_ERR_INVALID, "null buffer");
@@ -715,7 +962,7 @@ int nimble_constraint_force_jacobians_pw(nimble_world_t w, int32_t batch, const 
   hipStream_t st = (hipStream_t)stream;
   HIP_TRY(launchBackward(w, grid, st, batch, state, forces, const_cast<double*>(snapshot), nullptr, dfc_dstate,
                         dfc_dforces, rows, w->jacWsDoubles > 0 ? workspace : nullptr, w->jacWsDoubles, nullptr, 1, 1,
-                        body_inertia));
+                        body_inertia, ext));
   return NIMBLE_OK;
 }
 

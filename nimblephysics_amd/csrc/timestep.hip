@@ -24,6 +24,7 @@
 #include "stamp.cuh"
 #include "chol_wave.cuh"
 #include "inertia.cuh"
+#include "wrench.cuh"
 
 #define WAVE 64
 
@@ -36,18 +37,28 @@
 // how many callers the code object has: with both sets in one code object
 // nimble_backward_wide_kernel came out scheduled differently from the
 // library without the per-world path (the other four were the same), apart
-// they are instruction for instruction what they were.  A host build (the
-// wavefront emulation of tests/cpp/wave_emu, one translation unit with
-// capi.cpp) has no code object to keep apart and takes both sets.
+// they are instruction for instruction what they were.  timestep_ext.hip
+// does the same with NIMBLE_EXT_WRENCH_KERNELS for the instances that take
+// external body wrenches (body_wrench, wrench.cuh; template parameter kExt).
+// A host build (the wavefront emulation of tests/cpp/wave_emu, one
+// translation unit with capi.cpp) has no code object to keep apart and takes
+// all sets.
 #if defined(NIMBLE_PER_WORLD_KERNELS)
 #define NIMBLE_SHARED_MODEL_INSTANCES 0
 #define NIMBLE_PER_WORLD_INSTANCES 1
+#define NIMBLE_EXT_WRENCH_INSTANCES 0
+#elif defined(NIMBLE_EXT_WRENCH_KERNELS)
+#define NIMBLE_SHARED_MODEL_INSTANCES 0
+#define NIMBLE_PER_WORLD_INSTANCES 0
+#define NIMBLE_EXT_WRENCH_INSTANCES 1
 #elif defined(__HIP__)
 #define NIMBLE_SHARED_MODEL_INSTANCES 1
 #define NIMBLE_PER_WORLD_INSTANCES 0
+#define NIMBLE_EXT_WRENCH_INSTANCES 0
 #else
 #define NIMBLE_SHARED_MODEL_INSTANCES 1
 #define NIMBLE_PER_WORLD_INSTANCES 1
+#define NIMBLE_EXT_WRENCH_INSTANCES 1
 #endif
 
 // ---------------------------------------------------------------------------
@@ -223,9 +234,14 @@ __device__ __forceinline__ void worldInertia(const ModelDev& md, const double* b
 // Composite inertias IC[b] (subtree sums) and bias forces F[b] = sum over the
 // subtree of  I_i (A_i - a_g) + V_i x* (I_i V_i)  -- the world-frame
 // restatement of BodyNode::updateTransmittedForceID (BodyNode.cpp:1994).
-template <bool kPW = false>
+// kExt: the body's external wrench (`bw`: the world's [nb][6] block of
+// body_wrench, `frame` its frame flag; wrench.cuh), taken to the world frame,
+// is subtracted from the body's force before the subtree sums -- the
+// reference's `- mFext` in the bias force (BodyNode.cpp:2079) -- so the
+// generalized bias C holds -tau_ext = -sum_b J_b^T W_b.
+template <bool kPW = false, bool kExt = false>
 __device__ __forceinline__ void composites(const ModelDev& md, double* s, const Layout& L, int lane,
-                                           const double* bi = nullptr) {
+                                           const double* bi = nullptr, const double* bw = nullptr, int frame = 0) {
   const double ag[6] = {0, 0, 0, md.g[0], md.g[1], md.g[2]};
   if (lane < md.nb) {
     const int b = lane;
@@ -237,6 +253,11 @@ __device__ __forceinline__ void composites(const ModelDev& md, double* s, const 
     mv6(I, s + L.V + 6 * b, h);
     crf(s + L.V + 6 * b, h, vxh);
     for (int i = 0; i < 6; i++) s[L.F + 6 * b + i] = f[i] + vxh[i];
+    if constexpr (kExt) {
+      double ext[6];
+      worldWrench(bw + 6 * b, frame, s + L.Tw + 12 * b, ext);
+      for (int i = 0; i < 6; i++) s[L.F + 6 * b + i] -= ext[i];
+    }
   }
   WSYNC();
   // subtree sums: lane = one of the 42 entries (IC 36, F 6), walking the
@@ -367,14 +388,22 @@ __device__ __forceinline__ void coreDynamics(const ModelDev& md, double* s, cons
 // 21 frictional contacts) to the R = 2 kernel launched after it, which
 // steps only those worlds, from the same inputs.
 // kPW: the world's bodies take their inertial parameters from its rows of
-// `bodyInertia` ([batch][nb][10], inertia.cuh) instead of the model.
-template <int R, bool kMesh = false, bool kPW = false>
+// `bodyInertia` ([batch][nb][10], inertia.cuh) instead of the model; world
+// `env`'s block starts at env * inertiaStride (the kPW-only instances pass
+// none and take nb * 10; 0: one block for every world).
+// kExt: the world's bodies are pushed by its rows of `bodyWrench`
+// ([batch][nb][6], frame flag `wrenchFrame`; wrench.cuh), through the bias
+// force (composites), so the unconstrained velocity, the LCP's b and the
+// dynamics cache -- and with it the wide kernel -- see them.
+template <int R, bool kMesh = false, bool kPW = false, bool kExt = false>
 __device__ __forceinline__ void forwardWorld(const ModelDev* __restrict__ mdp, const Layout& L,
                                              const double* __restrict__ state, const double* __restrict__ forces,
                                              double* __restrict__ lcpCache, double* __restrict__ nextState,
                                              double* __restrict__ snapshot, int snapDoubles, int cacheDoubles,
                                              int deferRows, int env, bool deferLists,
-                                             const double* __restrict__ bodyInertia = nullptr) {
+                                             const double* __restrict__ bodyInertia = nullptr,
+                                             const double* __restrict__ bodyWrench = nullptr, int wrenchFrame = 0,
+                                             int inertiaStride = -1) {
   extern __shared__ double s[];
   const ModelDev& md = *mdp;
   const int lane = threadIdx.x & (WAVE - 1);
@@ -468,7 +497,11 @@ __device__ __forceinline__ void forwardWorld(const ModelDev* __restrict__ mdp, c
     // body transforms final: the helper wave detects the contacts meanwhile
     if (helperOn) collidePost(lds<true>(s) + L.ct, CS_GO, lane);
     STAMP(14);
-    composites<kPW>(md, s, L, lane, kPW ? bodyInertia + (size_t)env * md.nb * 10 : nullptr);
+    if constexpr (kExt)
+      composites<kPW, true>(md, s, L, lane, bodyInertia + (size_t)env * inertiaStride,
+                            bodyWrench + (size_t)env * md.nb * 6, wrenchFrame);
+    else
+      composites<kPW>(md, s, L, lane, kPW ? bodyInertia + (size_t)env * md.nb * 10 : nullptr);
     STAMP(15);
     massMatrixAndBias(md, s, L, lane, s + L.rhs);
     STAMP(16);
@@ -692,9 +725,20 @@ __device__ __forceinline__ void fdBlocksVjp(const double* s, const Layout& L, in
 // (Skeleton::getJacobianOfID, DifferentiableContactConstraint / BackpropSnapshot
 // use) contracted with w, collapsed to O(nb) 6-vector work; the identity is
 // checked against central differences in tools/proto/adjoint_rnea.py.
-template <bool kPW = false>
+// kExt (external body wrenches, wrench.cuh): the inverse dynamics is
+// ID - tau_ext with tau_ext = sum_b J_b^T E_b, E_b the world-frame wrench on
+// body b, so w^T tau_ext = sum_b W_b . E_b.  Its q-derivative has two parts.
+// W_b depends on q through the S_i: that is the derivative of S_k . F at
+// fixed F, which kappa carries once f_b holds -E_b.  A wrench given in the
+// body frame moves with the body: for b in the subtree of dof k,
+// dE_b/dq_k = Z_k x* E_b, and W . (Z x* E) = -Z . (W x* E), so
+// w^T d(-tau_ext)/dq_k = Z_k . sum_subtree W_b x* E_b: alpha, which enters
+// with a minus sign, becomes W x* (p - E).  A world-frame wrench is constant
+// in q and leaves alpha alone.
+template <bool kPW = false, bool kExt = false>
 __device__ __forceinline__ void adjointVectors(const ModelDev& md, double* s, const Layout& L, int lane,
-                                               const double* bi = nullptr) {
+                                               const double* bi = nullptr, const double* bw = nullptr,
+                                               int frame = 0) {
   const double ag[6] = {0, 0, 0, md.g[0], md.g[1], md.g[2]};
   const int nb = md.nb, n = md.n;
   if (lane < nb) {
@@ -718,6 +762,13 @@ __device__ __forceinline__ void adjointVectors(const ModelDev& md, double* s, co
       s[L.Wt + 6 * b + i] = W[i];
     }
     double* a = s + L.adj + 42 * b;
+    if constexpr (kExt) {
+      double ext[6];
+      worldWrench(bw + 6 * b, frame, s + L.Tw + 12 * b, ext);
+      for (int i = 0; i < 6; i++) s[L.F + 6 * b + i] -= ext[i];
+      if (frame == NIMBLE_WRENCH_BODY)
+        for (int i = 0; i < 6; i++) p[i] -= ext[i];  // (p's other uses are above)
+    }
     crf(W, p, a);           // alpha
     mv6(I, W, a + 6);       // beta
     crf(V, a + 6, t);
@@ -795,8 +846,16 @@ __device__ void rightJacobianCol(const double* th, int k, double* o) {
 // most `deferRows` LCP rows, the R = 2 kernel the others.
 // kPW: item (world, row) reads its world's rows of `bodyInertia`
 // ([batch][nb][10], inertia.cuh) wherever the model's mass, COM and moment
-// are read otherwise.
-template <int R, bool kPW = false>
+// are read otherwise (its block starts at env * inertiaStride; the kPW-only
+// instances pass none and take nb * 10).
+// kExt: the item's world is pushed by its rows of `bodyWrench` ([batch][nb][6],
+// frame flag `wrenchFrame`; wrench.cuh): they enter f_b and alpha
+// (adjointVectors); a* and rhs hold them already (the dynamics cache).
+// `gradWrench` ([items][nb][6], nullptr to skip): dt * Wt[b], the world twist
+// of body b under the unclipped w (after the contact prep: w - nu), in the
+// frame of the input -- the gradient with respect to the wrench on body b
+// (tau_ext is linear in it: d(w^T tau_ext)/dE_b = W_b), never clipped.
+template <int R, bool kPW = false, bool kExt = false>
 __device__ __forceinline__ void backwardItems(const ModelDev* __restrict__ mdp, int batch,
                                               const double* __restrict__ state, const double* __restrict__ forces,
                                               double* __restrict__ snapshot, int snapDoubles,
@@ -804,7 +863,9 @@ __device__ __forceinline__ void backwardItems(const ModelDev* __restrict__ mdp, 
                                               double* __restrict__ gradForces, int rows, double* __restrict__ ws,
                                               int wsDoubles, double* __restrict__ gradMasses, int fcMode,
                                               int massParams, int deferRows,
-                                              const double* __restrict__ bodyInertia = nullptr) {
+                                              const double* __restrict__ bodyInertia = nullptr,
+                                              const double* __restrict__ bodyWrench = nullptr, int wrenchFrame = 0,
+                                              double* __restrict__ gradWrench = nullptr, int inertiaStride = -1) {
   extern __shared__ double s[];
   const ModelDev& md = *mdp;
   const Layout& L = md.lay[1];
@@ -826,6 +887,9 @@ __device__ __forceinline__ void backwardItems(const ModelDev* __restrict__ mdp, 
     if (fcMode && (md.numPairs == 0 || unitRow >= uni((int)snapshot[(size_t)env * snapDoubles + SN_NC]))) {
       for (int i = lane; i < 2 * n; i += WAVE) gradState[(size_t)item * 2 * n + i] = 0.0;
       for (int i = lane; i < n; i += WAVE) gradForces[(size_t)item * n + i] = 0.0;
+      if constexpr (kExt)
+        if (gradWrench != nullptr)
+          for (int i = lane; i < 6 * md.nb; i += WAVE) gradWrench[(size_t)item * 6 * md.nb + i] = 0.0;
       continue;
     }
     loadState(md, s, L, lane, state + (size_t)env * 2 * n, forces + (size_t)env * n);
@@ -843,7 +907,9 @@ __device__ __forceinline__ void backwardItems(const ModelDev* __restrict__ mdp, 
         s[L.gv + i] = n + i == unitRow ? 1.0 : 0.0;
       }
     }
-    const double* bi = kPW ? bodyInertia + (size_t)env * md.nb * 10 : nullptr;
+    const double* bi = !kPW ? nullptr
+                       : kExt ? bodyInertia + (size_t)env * inertiaStride
+                              : bodyInertia + (size_t)env * md.nb * 10;
     double* sn = snapshot + (size_t)env * snapDoubles;
     double* hbmWs = ws != nullptr ? ws + (size_t)blockIdx.x * wsDoubles : sn + snapWorkspaceOffset(n);
     dynCacheCopy(md, s, L, sn + L.snDyn, false, lane);  // the forward's kinematics, L, C
@@ -886,7 +952,19 @@ __device__ __forceinline__ void backwardItems(const ModelDev* __restrict__ mdp, 
     }
     STAMP(22);
     accelerations(md, s, L, lane, x, s + L.adj);  // A = accelerations at a* (adjoint area not yet in use)
-    adjointVectors<kPW>(md, s, L, lane, bi);
+    if constexpr (kExt) {
+      adjointVectors<kPW, true>(md, s, L, lane, bi, bodyWrench + (size_t)env * md.nb * 6, wrenchFrame);
+      // (Wt is overwritten by the M-derivative fields below)
+      if (gradWrench != nullptr && lane < md.nb) {
+        const int b = lane;
+        double Wd[6], gw[6];
+        for (int i = 0; i < 6; i++) Wd[i] = dt * s[L.Wt + 6 * b + i];
+        twistInWrenchFrame(Wd, wrenchFrame, s + L.Tw + 12 * b, gw);
+        for (int i = 0; i < 6; i++) gradWrench[((size_t)item * md.nb + b) * 6 + i] = gw[i];
+      }
+    } else {
+      adjointVectors<kPW>(md, s, L, lane, bi);
+    }
     STAMP(23);
 
     // ---- per-direction columns -------------------------------------------
@@ -1202,3 +1280,61 @@ nimble_backward_wide_pw_kernel(const ModelDev* __restrict__ mdp, int batch, cons
                          wsDoubles, gradMasses, fcMode, massParams, deferRows, bodyInertia);
 }
 #endif  // NIMBLE_PER_WORLD_INSTANCES
+
+#if NIMBLE_EXT_WRENCH_INSTANCES
+// The instances that take external body wrenches (the `_ext` entry points):
+// bodyWrench [batch][nb][6] with its frame flag, and per-world body inertial
+// parameters as well -- kPW is always set here; for the model's own values
+// the entry point passes one [nb][10] block of them and inertiaStride 0
+// (else nb * 10).  The wide forward needs no instance: it reloads the bias
+// the one-row kernel cached, which holds the wrench.
+extern "C" __global__ void __launch_bounds__(2 * WAVE) __attribute__((amdgpu_waves_per_eu(2)))
+nimble_forward_ext_kernel(const ModelDev* __restrict__ mdp, Layout L, const double* __restrict__ state,
+                          const double* __restrict__ forces, double* __restrict__ lcpCache,
+                          double* __restrict__ nextState, double* __restrict__ snapshot, int snapDoubles,
+                          int cacheDoubles, int deferRows, int deferLists, const double* __restrict__ bodyInertia,
+                          int inertiaStride, const double* __restrict__ bodyWrench, int wrenchFrame) {
+  forwardWorld<1, false, true, true>(mdp, L, state, forces, lcpCache, nextState, snapshot, snapDoubles, cacheDoubles,
+                                     deferRows, blockIdx.x, deferLists != 0, bodyInertia, bodyWrench, wrenchFrame,
+                                     inertiaStride);
+}
+
+extern "C" __global__ void __launch_bounds__(2 * WAVE) __attribute__((amdgpu_waves_per_eu(2)))
+nimble_forward_mesh_ext_kernel(const ModelDev* __restrict__ mdp, Layout L, const double* __restrict__ state,
+                               const double* __restrict__ forces, double* __restrict__ lcpCache,
+                               double* __restrict__ nextState, double* __restrict__ snapshot, int snapDoubles,
+                               int cacheDoubles, int deferRows, int deferLists,
+                               const double* __restrict__ bodyInertia, int inertiaStride,
+                               const double* __restrict__ bodyWrench, int wrenchFrame) {
+  forwardWorld<1, true, true, true>(mdp, L, state, forces, lcpCache, nextState, snapshot, snapDoubles, cacheDoubles,
+                                    deferRows, blockIdx.x, deferLists != 0, bodyInertia, bodyWrench, wrenchFrame,
+                                    inertiaStride);
+}
+
+extern "C" __global__ void __launch_bounds__(WAVE)
+nimble_backward_ext_kernel(const ModelDev* __restrict__ mdp, int batch, const double* __restrict__ state,
+                           const double* __restrict__ forces, double* __restrict__ snapshot, int snapDoubles,
+                           const double* __restrict__ gradNext, double* __restrict__ gradState,
+                           double* __restrict__ gradForces, int rows, double* __restrict__ ws, int wsDoubles,
+                           double* __restrict__ gradMasses, int fcMode, int massParams, int deferRows,
+                           const double* __restrict__ bodyInertia, int inertiaStride,
+                           const double* __restrict__ bodyWrench, int wrenchFrame, double* __restrict__ gradWrench) {
+  backwardItems<1, true, true>(mdp, batch, state, forces, snapshot, snapDoubles, gradNext, gradState, gradForces, rows,
+                               ws, wsDoubles, gradMasses, fcMode, massParams, deferRows, bodyInertia, bodyWrench,
+                               wrenchFrame, gradWrench, inertiaStride);
+}
+
+extern "C" __global__ void __launch_bounds__(WAVE)
+nimble_backward_wide_ext_kernel(const ModelDev* __restrict__ mdp, int batch, const double* __restrict__ state,
+                                const double* __restrict__ forces, double* __restrict__ snapshot, int snapDoubles,
+                                const double* __restrict__ gradNext, double* __restrict__ gradState,
+                                double* __restrict__ gradForces, int rows, double* __restrict__ ws, int wsDoubles,
+                                double* __restrict__ gradMasses, int fcMode, int massParams, int deferRows,
+                                const double* __restrict__ bodyInertia, int inertiaStride,
+                                const double* __restrict__ bodyWrench, int wrenchFrame,
+                                double* __restrict__ gradWrench) {
+  backwardItems<2, true, true>(mdp, batch, state, forces, snapshot, snapDoubles, gradNext, gradState, gradForces, rows,
+                               ws, wsDoubles, gradMasses, fcMode, massParams, deferRows, bodyInertia, bodyWrench,
+                               wrenchFrame, gradWrench, inertiaStride);
+}
+#endif  // NIMBLE_EXT_WRENCH_INSTANCES

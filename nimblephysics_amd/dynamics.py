@@ -424,6 +424,74 @@ class BodyNode:
         self.restitution = float(r)
         _model_changed(self.skel)
 
+    # --- external forces (BodyNode.cpp:1532-1612) ------------------------------
+    # mFext: the body-frame wrench [torque xyz, force xyz] about the body
+    # frame's origin that the next step applies (bias force, BodyNode.cpp:2079)
+    # and World::step clears (World.cpp:300).  An input of the step, not part
+    # of the model: the setters leave the device model as it is.  The
+    # world-frame variants need the body's world transform, which only the
+    # device computes: pass a world-frame wrench to the step itself instead
+    # (``timestep(..., body_wrench=, wrench_frame="world")``).
+    _NON_LOCAL = ("needs the body's world transform on the host; give the step a world-frame wrench instead: "
+                  "timestep(..., body_wrench=W, wrench_frame=\"world\")")
+
+    def _fext(self) -> np.ndarray:
+        f = self.__dict__.get("_ext_wrench")
+        if f is None:
+            f = self._ext_wrench = np.zeros(6)
+        return f
+
+    def setExtWrench(self, wrench):
+        """BodyNode::setExtWrench (BodyNode.cpp:1585): mFext = wrench."""
+        w = np.asarray(wrench, dtype=np.float64)
+        if w.shape != (6,):
+            raise ValueError(f"wrench must be 6 values [torque xyz, force xyz], got shape {w.shape}")
+        self._ext_wrench = w.copy()
+
+    def getExternalForceLocal(self):
+        """BodyNode::getExternalForceLocal: mFext."""
+        return self._fext().copy()
+
+    def clearExternalForces(self):
+        """BodyNode::clearExternalForces: mFext = 0."""
+        self._ext_wrench = np.zeros(6)
+
+    @staticmethod
+    def _point_force(force, offset):
+        # math::dAdInvT(T(offset), [0; f]) = [offset x f; f]
+        f = np.asarray(force, dtype=np.float64).reshape(3)
+        o = np.asarray(offset, dtype=np.float64).reshape(3)
+        return np.concatenate([np.cross(o, f), f])
+
+    def addExtForce(self, force, offset=(0.0, 0.0, 0.0), isForceLocal=False, isOffsetLocal=True):
+        """BodyNode::addExtForce (BodyNode.cpp:1532) for a body-frame force at
+        a body-frame point (isForceLocal=True, isOffsetLocal=True)."""
+        if not (isForceLocal and isOffsetLocal):
+            raise NotImplementedError("addExtForce with a world-frame force or offset " + self._NON_LOCAL)
+        self._ext_wrench = self._fext() + self._point_force(force, offset)
+
+    def setExtForce(self, force, offset=(0.0, 0.0, 0.0), isForceLocal=False, isOffsetLocal=True):
+        """BodyNode::setExtForce (BodyNode.cpp:1558): replaces mFext."""
+        if not (isForceLocal and isOffsetLocal):
+            raise NotImplementedError("setExtForce with a world-frame force or offset " + self._NON_LOCAL)
+        self._ext_wrench = self._point_force(force, offset)
+
+    def addExtTorque(self, torque, _isLocal=False):
+        """BodyNode::addExtTorque (BodyNode.cpp:1593), body-frame torque."""
+        if not _isLocal:
+            raise NotImplementedError("addExtTorque with a world-frame torque " + self._NON_LOCAL)
+        f = self._fext().copy()
+        f[:3] += np.asarray(torque, dtype=np.float64).reshape(3)
+        self._ext_wrench = f
+
+    def setExtTorque(self, torque, _isLocal=False):
+        """BodyNode::setExtTorque (BodyNode.cpp:1605): replaces the torque part."""
+        if not _isLocal:
+            raise NotImplementedError("setExtTorque with a world-frame torque " + self._NON_LOCAL)
+        f = self._fext().copy()
+        f[:3] = np.asarray(torque, dtype=np.float64).reshape(3)
+        self._ext_wrench = f
+
     def createShapeNode(self, shape: Shape, collision: bool = False):
         node = ShapeNode(self, shape, collision)
         self.shape_nodes.append(node)
@@ -532,6 +600,11 @@ class Skeleton:
 
     def getRootBodyNode(self):
         return self.bodies[0]
+
+    def clearExternalForces(self):
+        """Skeleton::clearExternalForces: every body's mFext = 0."""
+        for b in self.bodies:
+            b.clearExternalForces()
 
     def setMobile(self, mobile: bool):
         self.mobile = bool(mobile)

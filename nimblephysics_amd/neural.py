@@ -48,13 +48,23 @@ class LossGradientHighLevelAPI:
         self.lossWrtState = None
         self.lossWrtAction = None
         self.lossWrtMass = None
+        # the gradient with respect to the step's external body wrenches
+        # ([nBodies, 6] in the world's body order and the frame of the input;
+        # None for a step without wrenches)
+        self.lossWrtBodyWrench = None
 
 
 class BackpropSnapshot:
     """The batched BackpropSnapshot of one forward launch over B worlds."""
 
-    def __init__(self, world: World, dev, state, forces, next_state, snapshot, single: bool, body_inertia=None):
+    def __init__(self, world: World, dev, state, forces, next_state, snapshot, single: bool, body_inertia=None,
+                 body_wrench=None, wrench_frame=0):
         self._world = world
+        # the step's external body wrenches ([B, num_bodies, 6] in device-model
+        # order, or None) and their frame flag, kept like the parameters
+        self._wrench = body_wrench
+        self._wrench_frame = wrench_frame
+        self._wjac = None
         # the step's per-world body parameters ([B, num_bodies, 10], or None
         # for the model's own): every derivative of the step reads them again
         self._inertia = body_inertia
@@ -86,9 +96,26 @@ class BackpropSnapshot:
         if self._jac is None:
             with torch.cuda.device(self._state.device):
                 stream = torch.cuda.current_stream(self._state.device).cuda_stream
-                self._jac = self._dev.jacobians(self._state, self._forces, self._snap, stream,
+                if self._wrench is None:
+                    self._jac = self._dev.jacobians(self._state, self._forces, self._snap, stream,
                                                     body_inertia=self._inertia)
+                else:
+                    J, F, W = self._dev.jacobians(self._state, self._forces, self._snap, stream,
+                                                  body_inertia=self._inertia, body_wrench=self._wrench,
+                                                  wrench_frame=self._wrench_frame, wrench_jacobian=True)
+                    self._jac, self._wjac = (J, F), W
         return self._jac
+
+    def getBodyWrenchJacobian(self, world: Optional[World] = None):
+        """d(next state)/d(body_wrench): [2n, nBodies, 6] ([B, ...] batched),
+        bodies in the world's body order, in the frame of the step's wrench
+        input (DifferentiableExternalForce::getJacobianOfTauWrtWorldWrench
+        taken through the step)."""
+        self._check_world(world)
+        if self._wrench is None:
+            raise ValueError("this step had no external body wrenches (forwardPass(..., body_wrench=))")
+        self._jacobians()
+        return self._out(self._world._gather_wrench(self._wjac))
 
     # --- Jacobians (BackpropSnapshot.cpp) ---------------------------------------
     def getStateJacobian(self, world: Optional[World] = None):
@@ -166,8 +193,10 @@ class BackpropSnapshot:
         if self._fcjac is None:
             with torch.cuda.device(self._state.device):
                 stream = torch.cuda.current_stream(self._state.device).cuda_stream
+                extra = {} if self._wrench is None else {"body_wrench": self._wrench,
+                                                         "wrench_frame": self._wrench_frame}
                 self._fcjac = self._dev.constraint_force_jacobians(self._state, self._forces, self._snap, stream,
-                                                                       body_inertia=self._inertia)
+                                                                       body_inertia=self._inertia, **extra)
         Js, Jf = self._fcjac
         n = self._n
         J = {"POSITION": Js[:, :, :n], "VELOCITY": Js[:, :, n:], "FORCE": Jf}.get(kind)
@@ -179,35 +208,50 @@ class BackpropSnapshot:
 
     # --- backprop (BackpropSnapshot.cpp:121, :382) ------------------------------
     def _vjp(self, grad_next):
-        """(lossWrtState, lossWrtForces, lossWrtMass): the mass part is
-        getMassVelJacobian^T dL/dv' (BackpropSnapshot.cpp:177, :418) for the
-        world's tuned masses, [B, getMassDims()]."""
+        """(lossWrtState, lossWrtForces, lossWrtMass, lossWrtBodyWrench): the
+        mass part is getMassVelJacobian^T dL/dv' (BackpropSnapshot.cpp:177,
+        :418) for the world's tuned masses, [B, getMassDims()]; the wrench
+        part [B, nBodies, 6] (None for a step without wrenches)."""
         g = grad_next.reshape(self._state.shape).to(self._state.device, torch.float64).contiguous()
         gs = torch.empty_like(self._state)
         gf = torch.empty_like(self._forces)
         B = self._state.shape[0]
         with torch.cuda.device(self._state.device):
             stream = torch.cuda.current_stream(self._state.device).cuda_stream
-            if self._world.getMassDims() > 0:
+            gw = None
+            if self._wrench is not None:
+                gw = torch.empty_like(self._wrench)
+                wr = {"body_wrench": self._wrench, "wrench_frame": self._wrench_frame}
+                if self._world.getMassDims() > 0:
+                    gm = mass_gradient(self._dev, self._world._mass_selection(), self._state, self._forces,
+                                       self._snap, g, gs, gf, stream, self._inertia, **wr)
+                else:
+                    gm = torch.zeros((B, 0), dtype=torch.float64, device=self._state.device)
+                # (the mass modes have no wrench output: the plain backward too)
+                self._dev.backward(self._state, self._forces, self._snap, g, gs, gf, stream, self._inertia,
+                                   grad_wrench=gw, **wr)
+                gw = self._world._gather_wrench(gw)
+            elif self._world.getMassDims() > 0:
                 gm = mass_gradient(self._dev, self._world._mass_selection(), self._state, self._forces, self._snap, g,
                                    gs, gf, stream, self._inertia)
             else:
                 extra = () if self._inertia is None else (self._inertia,)
                 self._dev.backward(self._state, self._forces, self._snap, g, gs, gf, stream, *extra)
                 gm = torch.zeros((B, 0), dtype=torch.float64, device=self._state.device)
-        return gs, gf, gm
+        return gs, gf, gm, gw
 
     def backpropState(self, world: Optional[World], nextTimestepStateLossGrad) -> LossGradientHighLevelAPI:
         """lossWrtState [2n], lossWrtAction [|A|], lossWrtMass [getMassDims()]."""
         self._check_world(world)
         g = torch.as_tensor(np.asarray(nextTimestepStateLossGrad) if not torch.is_tensor(nextTimestepStateLossGrad)
                             else nextTimestepStateLossGrad, dtype=torch.float64)
-        gs, gf, gm = self._vjp(g)
+        gs, gf, gm, gw = self._vjp(g)
         idx = _action_index(self._world, gf.device)
         out = LossGradientHighLevelAPI()
         out.lossWrtState = self._out(gs)
         out.lossWrtAction = self._out(gf.index_select(1, idx))
         out.lossWrtMass = self._out(gm)
+        out.lossWrtBodyWrench = None if gw is None else self._out(gw)
         return out
 
     def backprop(self, world: Optional[World], thisTimestepLoss: LossGradient, nextTimestepLoss: LossGradient):
@@ -220,7 +264,7 @@ class BackpropSnapshot:
             nextTimestepLoss.lossWrtVelocity) else nextTimestepLoss.lossWrtVelocity, dtype=torch.float64)
         B = self._state.shape[0]
         g = torch.cat([gp.reshape(B, -1), gv.reshape(B, -1)], dim=1)
-        gs, gf, gm = self._vjp(g)
+        gs, gf, gm, _ = self._vjp(g)
         n = self._n
         thisTimestepLoss.lossWrtPosition = self._out(gs[:, :n])
         thisTimestepLoss.lossWrtVelocity = self._out(gs[:, n:])
@@ -266,7 +310,8 @@ class BackpropSnapshot:
         return self._out(self._dev.status(self._snap))
 
 
-def forwardPass(world: World, idempotent: bool = False, state=None, action=None, mass=None) -> BackpropSnapshot:
+def forwardPass(world: World, idempotent: bool = False, state=None, action=None, mass=None, body_wrench=None,
+                wrench_frame="world") -> BackpropSnapshot:
     """neural::forwardPass (NeuralUtils.cpp:26).
 
     ``forwardPass(world)`` steps the world's own state and control forces (the
@@ -277,8 +322,19 @@ def forwardPass(world: World, idempotent: bool = False, state=None, action=None,
     untouched.  The batched form takes ``mass``, a [B, getMassDims()] tensor
     of per-world tuned values (see timestep): the snapshot keeps the expanded
     parameter array, its Jacobians and backprop are those of each world's own
-    parameters, and its lossWrtMass is [B, getMassDims()]."""
+    parameters, and its lossWrtMass is [B, getMassDims()].
+
+    ``body_wrench`` ([B, nBodies, 6] batched, [nBodies, 6] for
+    ``forwardPass(world)``; bodies in the world's body order, [torque xyz,
+    force xyz], in ``wrench_frame`` "world" or "body"; see timestep) pushes on
+    the bodies during the step.  The snapshot keeps it: backpropState returns
+    lossWrtBodyWrench and getBodyWrenchJacobian() the step's Jacobian with
+    respect to it.  Without it, ``forwardPass(world)`` applies the wrenches
+    stored on the world's bodies (BodyNode.setExtWrench ..., body frame) when
+    any is non-zero, and clears them after the step unless ``idempotent``
+    (World.cpp:300)."""
     bi = None
+    frame = _native.wrench_frame_flag(wrench_frame)
     if mass is not None and (state is None or state.dim() != 2):
         raise ValueError("forwardPass: a per-world mass needs the batched (2-D) state and action")
     if state is None:
@@ -286,6 +342,17 @@ def forwardPass(world: World, idempotent: bool = False, state=None, action=None,
         dev = _compute_device(torch.zeros(0))
         st = torch.tensor(world.getState(), dtype=torch.float64, device=dev).reshape(1, -1)
         act = torch.tensor(world.getAction(), dtype=torch.float64, device=dev).reshape(1, -1)
+        if body_wrench is None:
+            sw = world._stored_wrench()
+            if sw is not None:
+                body_wrench, frame = sw, _native.WRENCH_BODY
+        if body_wrench is not None:
+            body_wrench = torch.as_tensor(np.asarray(body_wrench) if not torch.is_tensor(body_wrench)
+                                          else body_wrench, dtype=torch.float64)
+            if tuple(body_wrench.shape) != (world.getNumBodyNodes(), 6):
+                raise ValueError(f"body_wrench must be [{world.getNumBodyNodes()}, 6] for forwardPass(world), got "
+                                 f"{tuple(body_wrench.shape)}")
+            body_wrench = body_wrench.unsqueeze(0)
     else:
         single = False
         if action is None:
@@ -303,11 +370,15 @@ def forwardPass(world: World, idempotent: bool = False, state=None, action=None,
                 raise ValueError(f"per-world mass must be [{st.shape[0]}, {world.getMassDims()}] (batch, the world's "
                                  f"tuned mass dims), got {tuple(mass.shape)}")
             bi = world._batched_inertia(mass.detach().to(dev, torch.float64))
+        if body_wrench is not None and (body_wrench.dim() != 3 or body_wrench.shape[0] != st.shape[0]):
+            raise ValueError(f"body_wrench must be [{st.shape[0]}, {world.getNumBodyNodes()}, 6] for this state, got "
+                             f"{tuple(body_wrench.shape)}")
+    bw = world._scatter_wrench(body_wrench.detach().to(dev, torch.float64)) if body_wrench is not None else None
     prev = getattr(world, "_batch_state", None)
     saved = prev.cache.clone() if (idempotent and prev is not None) else None
     try:
         with torch.cuda.device(dev):
-            devworld, forces, nxt, snap = step_batch(world, st, act, bi)
+            devworld, forces, nxt, snap = step_batch(world, st, act, bi, bw, frame)
     finally:
         if idempotent:
             # RestorableSnapshot: the LCP warm-start cache is part of the world
@@ -322,6 +393,7 @@ def forwardPass(world: World, idempotent: bool = False, state=None, action=None,
         out = nxt[0].cpu().numpy()
         world.setState(out)
         world.setControlForces(np.zeros(world.getNumDofs()))
-    snapshot = BackpropSnapshot(world, devworld, st, forces, nxt, snap, single, bi)
+        world.clearExternalForces()  # World::step (World.cpp:300)
+    snapshot = BackpropSnapshot(world, devworld, st, forces, nxt, snap, single, bi, bw, frame)
     world._cached_snapshot = snapshot
     return snapshot

@@ -356,6 +356,72 @@ class World:
             out[:, rows] = mass2d.detach().to(torch.float64).index_select(1, cols) * coef
         return out.reshape(B, -1, 10)
 
+    # --- external body wrenches (see timestep.py) -----------------------------
+    def _world_bodies(self):
+        """Every BodyNode in the world's body order: skeleton by skeleton,
+        each skeleton's bodies in order -- the rows of ``body_wrench``."""
+        return [b for s in self.skeletons for b in s.bodies]
+
+    def getNumBodyNodes(self) -> int:
+        return sum(len(s.bodies) for s in self.skeletons)
+
+    def _wrench_device_rows(self) -> np.ndarray:
+        """Device-model index of each body of _world_bodies(): the device
+        model also holds the massless frames of compound-joint chains
+        (_model_bodies), which take no wrench."""
+        rows = [k for k, e in enumerate(self._model_bodies()) if e[2] is not None]
+        return np.asarray(rows, dtype=np.int64)
+
+    def _scatter_wrench(self, wrench):
+        """[B, getNumBodyNodes(), 6] wrenches in the world's body order -> the
+        kernels' body_wrench [B, num_bodies, 6] in device-model order, on the
+        tensor's device with torch ops only; chain frames get zero rows."""
+        import torch
+        nbw = self.getNumBodyNodes()
+        if wrench.dim() != 3 or tuple(wrench.shape[1:]) != (nbw, 6):
+            raise ValueError(f"body_wrench must be [batch, {nbw}, 6] (the world's bodies, [torque xyz, force xyz]), "
+                             f"got {tuple(wrench.shape)}")
+        rows = self._wrench_device_rows()
+        nb = len(self._model_bodies())
+        w = wrench.detach().to(torch.float64)
+        if nb == nbw:
+            return w.contiguous()
+        out = torch.zeros((w.shape[0], nb, 6), dtype=torch.float64, device=w.device)
+        out.index_copy_(1, torch.as_tensor(rows, dtype=torch.long).to(w.device), w)
+        return out
+
+    def _gather_wrench(self, dev_wrench):
+        """The inverse selection: rows of a device-order [..., num_bodies, 6]
+        array for the world's bodies, [..., getNumBodyNodes(), 6]."""
+        import torch
+        rows = self._wrench_device_rows()
+        if len(rows) == dev_wrench.shape[-2]:
+            return dev_wrench
+        return dev_wrench.index_select(dev_wrench.dim() - 2, torch.as_tensor(rows, dtype=torch.long).to(dev_wrench.device))
+
+    def _stored_wrench(self) -> Optional[np.ndarray]:
+        """The bodies' stored mFext (BodyNode.setExtWrench and the other
+        setters) as [getNumBodyNodes(), 6], body frame; None when all are
+        zero, so that such a step takes the path without wrenches."""
+        w = np.array([b.getExternalForceLocal() for b in self._world_bodies()]).reshape(-1, 6)
+        return w if np.any(w != 0.0) else None
+
+    def clearExternalForces(self):
+        """Every body's mFext = 0, as World::step does after the step
+        (World.cpp:300)."""
+        for s in self.skeletons:
+            s.clearExternalForces()
+
+    def step(self, resetCommand: bool = True):
+        """World::step (World.cpp:221) on the world's own state: the device
+        step of neural.forwardPass(world); the bodies' stored external
+        wrenches are applied and cleared."""
+        from . import neural
+        f = self.getControlForces()
+        neural.forwardPass(self)
+        if not resetCommand:
+            self.setControlForces(f)
+
     def _model_bodies(self):
         """The device model's bodies in order: (skeleton index, skeleton,
         BodyNode or None, owning BodyNode, chain element): every BodyNode, a

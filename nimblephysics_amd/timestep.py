@@ -40,6 +40,27 @@ device model are left as they are, and nothing goes through the host.
 Nothing is validated on the device: a non-positive mass or an indefinite
 moment of inertia gives whatever the arithmetic gives (usually NaN from the
 Cholesky factor), without an error.
+
+External body wrenches: ``body_wrench`` pushes on the bodies during the step
+(the reference's BodyNode::mFext, BodyNode.cpp:1532-1612, and the worldWrench
+of DifferentiableExternalForce).  It is [B, nBodies, 6] with a 2-D state, or
+[nBodies, 6] with a 1-D state: one [torque xyz, force xyz] per body, bodies
+in the world's body order (skeleton by skeleton, each skeleton's BodyNodes in
+order; ``World.getNumBodyNodes()`` of them).  ``wrench_frame="world"``: world
+axes, moment about the world origin, constant in q; ``"body"``: body axes,
+moment about the body frame's origin, moving with the body (what
+``BodyNode.setExtWrench`` stores).  The rows are scattered on the device to
+the kernels' body order (World._scatter_wrench -> nimble_forward_ext's
+body_wrench; the massless frames of compound-joint chains get zero), and
+tau_ext = sum_b J_b^T W_b enters the step through the bias force, so contacts
+and every derivative see it.  ``body_wrench.grad`` has the shape of the input
+and is in its frame; the bound clipping of the action gradient does not apply
+to it.  It combines with 1-D and 2-D ``mass``.  When a mass gradient and a
+wrench gradient are both wanted the backward runs two launches (the mass /
+inertia modes have no wrench output).  Without an explicit ``body_wrench`` a
+1-D step applies the wrenches stored on the world's bodies (body frame), if
+any is non-zero, and clears them afterwards, as World::step does
+(World.cpp:300).  Nothing is validated on the device: a NaN wrench gives NaN.
 """
 from __future__ import annotations
 
@@ -47,7 +68,7 @@ from typing import Optional
 
 import torch
 
-from ._native import ContactCapacityError, ST_DIVERGES, status_message
+from ._native import ContactCapacityError, ST_DIVERGES, WRENCH_BODY, status_message, wrench_frame_flag
 from .simulation import World
 
 
@@ -131,13 +152,16 @@ def _check_status(world: World, dev, snap: torch.Tensor) -> None:
             f"their step would differ from the reference's (world.setStatusPolicy('record') to continue anyway)")
 
 
-def step_batch(world: World, st: torch.Tensor, act: torch.Tensor, body_inertia: Optional[torch.Tensor] = None):
+def step_batch(world: World, st: torch.Tensor, act: torch.Tensor, body_inertia: Optional[torch.Tensor] = None,
+               body_wrench: Optional[torch.Tensor] = None, wrench_frame="world"):
     """One batched forward launch (neural::forwardPass on every row of the
     2-D device tensors `st` [B, 2n] / `act` [B, |action space|]).  Returns
     (device world, forces [B, n], next state [B, 2n], snapshot [B, S]); the
     world's LCP warm-start caches advance and its status word is checked.
     `body_inertia` [B, num_bodies, 10]: per-world body parameters
-    (World._batched_inertia) instead of the model's."""
+    (World._batched_inertia) instead of the model's.  `body_wrench`
+    [B, num_bodies, 6] in device-model order (World._scatter_wrench) with its
+    `wrench_frame`: external body wrenches."""
     B = st.shape[0]
     n = world.getNumDofs()
     if st.shape[1] != 2 * n:
@@ -157,7 +181,10 @@ def step_batch(world: World, st: torch.Tensor, act: torch.Tensor, body_inertia: 
     stream = torch.cuda.current_stream(st.device).cuda_stream
     # (positional, and nothing extra on the shared path: callers may wrap the
     # device world's forward / backward, as bench.py's kernel timer does)
-    if body_inertia is None:
+    if body_wrench is not None:
+        dev.forward(st, forces, bs.cache, nxt, snap, stream, body_inertia, body_wrench=body_wrench,
+                    wrench_frame=wrench_frame)
+    elif body_inertia is None:
         dev.forward(st, forces, bs.cache, nxt, snap, stream)
     else:
         dev.forward(st, forces, bs.cache, nxt, snap, stream, body_inertia)
@@ -166,26 +193,37 @@ def step_batch(world: World, st: torch.Tensor, act: torch.Tensor, body_inertia: 
     return dev, forces, nxt, snap
 
 
-def mass_gradient(dev, selection, st, forces, snap, g, gs, gf, stream, body_inertia=None):
+def mass_gradient(dev, selection, st, forces, snap, g, gs, gf, stream, body_inertia=None, body_wrench=None,
+                  wrench_frame="world"):
     """lossWrtMass [B, getMassDims()] (with the state / force gradients into
     gs / gf): nimble_backward_masses when only body masses are tuned, else
     nimble_backward_inertia's ten parameters per body taken to the mass
     vector by World._mass_selection's matrix.  `body_inertia`: the per-world
-    parameters of the forward that wrote `snap` (the _pw entry points)."""
+    parameters of the forward that wrote `snap` (the _pw entry points);
+    `body_wrench` / `wrench_frame`: its external wrenches (the _ext ones)."""
     only_masses, sel = selection
     B = st.shape[0]
     if only_masses:
         gmb = torch.empty((B, dev.nb), dtype=torch.float64, device=st.device)
-        dev.backward_masses(st, forces, snap, g, gs, gf, gmb, stream, body_inertia=body_inertia)
+        if body_wrench is None:
+            dev.backward_masses(st, forces, snap, g, gs, gf, gmb, stream, body_inertia=body_inertia)
+        else:
+            dev.backward_masses(st, forces, snap, g, gs, gf, gmb, stream, body_inertia=body_inertia,
+                                body_wrench=body_wrench, wrench_frame=wrench_frame)
         return gmb.index_select(1, torch.tensor(sel, dtype=torch.long, device=st.device))
     gi = torch.empty((B, dev.nb, 10), dtype=torch.float64, device=st.device)
-    dev.backward_inertia(st, forces, snap, g, gs, gf, gi, stream, body_inertia=body_inertia)
+    if body_wrench is None:
+        dev.backward_inertia(st, forces, snap, g, gs, gf, gi, stream, body_inertia=body_inertia)
+    else:
+        dev.backward_inertia(st, forces, snap, g, gs, gf, gi, stream, body_inertia=body_inertia,
+                             body_wrench=body_wrench, wrench_frame=wrench_frame)
     return gi.reshape(B, dev.nb * 10) @ torch.as_tensor(sel, dtype=torch.float64, device=st.device)
 
 
 class TimestepLayer(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, world: World, state: torch.Tensor, action: torch.Tensor, mass: Optional[torch.Tensor]):
+    def forward(ctx, world: World, state: torch.Tensor, action: torch.Tensor, mass: Optional[torch.Tensor],
+                body_wrench: Optional[torch.Tensor] = None, wrench_frame="world"):
         # `mass` follows the reference (timestep.py:34, world.setMasses): the
         # world's getMassDims() tuned body masses, one vector for the batch
         ctx.use_mass = mass is not None
@@ -215,6 +253,22 @@ class TimestepLayer(torch.autograd.Function):
             ctx.mass_shape = tuple(mass.shape)
             ctx.mass_device = mass.device
             ctx.mass_sel = world._mass_selection()
+        # external body wrenches: the explicit argument, else (one world) what
+        # the bodies' setters stored, body frame; a zero stored wrench takes
+        # the path without wrenches
+        frame = 0
+        ctx.wrench_explicit = body_wrench is not None
+        if body_wrench is not None:
+            frame = wrench_frame_flag(wrench_frame)
+            want = (world.getNumBodyNodes(), 6) if state.dim() == 1 else (state.shape[0], world.getNumBodyNodes(), 6)
+            if tuple(body_wrench.shape) != want:
+                raise ValueError(f"body_wrench must be {list(want)} for this state ([torque xyz, force xyz] per body "
+                                 f"of the world), got {tuple(body_wrench.shape)}")
+            ctx.wrench_device = body_wrench.device
+        elif state.dim() == 1:
+            sw = world._stored_wrench()
+            if sw is not None:
+                body_wrench, frame = torch.as_tensor(sw, dtype=torch.float64), WRENCH_BODY
         ctx.out_device = state.device
         cdev = _compute_device(state)
         with torch.cuda.device(cdev):
@@ -226,8 +280,16 @@ class TimestepLayer(torch.autograd.Function):
             st = st.contiguous()
             n = world.getNumDofs()
             bi = world._batched_inertia(mass.detach().to(cdev, torch.float64)) if ctx.per_world else None
-            dev, forces, nxt, snap = step_batch(world, st, act, bi)
+            bw = None
+            if body_wrench is not None:
+                w3 = body_wrench.detach().to(cdev, torch.float64)
+                bw = world._scatter_wrench(w3.unsqueeze(0) if squeeze else w3)
+            dev, forces, nxt, snap = step_batch(world, st, act, bi, bw, frame)
             idx = _action_index(world, st.device)
+        if squeeze:
+            world.clearExternalForces()  # World::step (World.cpp:300)
+        ctx.body_wrench = bw
+        ctx.wrench_frame = frame
         ctx.world = world
         ctx.identity = _identity_action(world, world.getNumDofs())
         # the backward must run on the model (and snapshot layout) that
@@ -258,11 +320,27 @@ class TimestepLayer(torch.autograd.Function):
             gf = torch.empty_like(forces)
             stream = torch.cuda.current_stream(st.device).cuda_stream
             gm = None
+            gw = None
             bi = ctx.body_inertia
+            bw, frame = ctx.body_wrench, ctx.wrench_frame
+            want_gw = ctx.wrench_explicit and ctx.needs_input_grad[4]
+            if want_gw:
+                gw = torch.empty_like(bw)
             if ctx.per_world and ctx.mass_shape[1] > 0:
-                gm = mass_gradient(dev, ctx.mass_sel, st, forces, snap, g, gs, gf, stream, bi).to(ctx.mass_device)
+                gm = mass_gradient(dev, ctx.mass_sel, st, forces, snap, g, gs, gf, stream, bi, bw,
+                                   frame).to(ctx.mass_device)
+                if want_gw:  # (the mass modes have no wrench output)
+                    dev.backward(st, forces, snap, g, gs, gf, stream, bi, body_wrench=bw, wrench_frame=frame,
+                                 grad_wrench=gw)
             elif ctx.use_mass and not ctx.per_world and ctx.mass_shape[0] > 0:
-                gm = mass_gradient(dev, ctx.mass_sel, st, forces, snap, g, gs, gf, stream).sum(0).to(ctx.mass_device)
+                gm = mass_gradient(dev, ctx.mass_sel, st, forces, snap, g, gs, gf, stream, None, bw,
+                                   frame).sum(0).to(ctx.mass_device)
+                if want_gw:
+                    dev.backward(st, forces, snap, g, gs, gf, stream, bi, body_wrench=bw, wrench_frame=frame,
+                                 grad_wrench=gw)
+            elif bw is not None:
+                dev.backward(st, forces, snap, g, gs, gf, stream, bi, body_wrench=bw, wrench_frame=frame,
+                             grad_wrench=gw)
             elif bi is None:
                 dev.backward(st, forces, snap, g, gs, gf, stream)
             else:
@@ -271,12 +349,16 @@ class TimestepLayer(torch.autograd.Function):
         od = ctx.out_device
         if ctx.use_mass and gm is None:
             gm = torch.zeros(ctx.mass_shape, dtype=torch.float64, device=ctx.mass_device)
+        if gw is not None:
+            gw = ctx.world._gather_wrench(gw)
+            gw = (gw[0] if ctx.squeeze else gw).to(ctx.wrench_device)
         if ctx.squeeze:
-            return None, gs[0].to(od), ga[0].to(od), gm
-        return None, gs.to(od), ga.to(od), gm
+            return None, gs[0].to(od), ga[0].to(od), gm, gw, None
+        return None, gs.to(od), ga.to(od), gm, gw, None
 
 
 def timestep(world: World, state: torch.Tensor, action: torch.Tensor,
-             mass: Optional[torch.Tensor] = None) -> torch.Tensor:
+             mass: Optional[torch.Tensor] = None, body_wrench: Optional[torch.Tensor] = None,
+             wrench_frame="world") -> torch.Tensor:
     """Differentiable step; see module docstring."""
-    return TimestepLayer.apply(world, state, action, mass)
+    return TimestepLayer.apply(world, state, action, mass, body_wrench, wrench_frame)
