@@ -415,6 +415,62 @@ int nimble_constraint_force_jacobians_ext(nimble_world_t world, int32_t batch, c
                                           const double* body_wrench, int32_t wrench_frame,
                                           void* stream);
 
+/*
+ * Batched inverse dynamics: which joint forces produce this motion?
+ *
+ *   tau = ID(q, v, a) = M(q) a + C(q, v) - tau_ext(q) + D v + K (q - q0 + dt v)
+ *
+ * == Skeleton::getInverseDynamics (dart/dynamics/Skeleton.cpp:9433:
+ * multiplyByImplicitMassMatrix :11124, getDampingForce :11355, getSpringForce
+ * :11388, - getExternalForces()), taken over all of the world's dofs instead
+ * of one skeleton's.  Every term is in the step's conventions: (q | v) is a
+ * row of `state`, for free and ball joints v and a are the body-twist
+ * coordinates the step uses, C holds gravity, tau_ext is the generalized
+ * force of body_wrench exactly as in nimble_forward_ext, D / K / q0 are the
+ * description's damping, spring and rest_position.  tau is the exact inverse
+ * of the contact-free step: nimble_forward with forces = tau has
+ * v' = v + dt a.  Contacts play no part: a model with collision pairs gets
+ * the answer it would get without them.
+ *   state        [batch][2*num_dofs]   device
+ *   ddq          [batch][num_dofs]     the accelerations a, device
+ *   body_inertia [batch][num_bodies][10] or NULL (the model's values), as for
+ *                the `_pw` entry points
+ *   body_wrench  [batch][num_bodies][6] or NULL (none), wrench_frame as for
+ *                the `_ext` entry points
+ *   tau          [batch][num_dofs]     output, over all dofs
+ *   mass_matrix  [batch][num_dofs][num_dofs] output or NULL: M(q), full
+ *                symmetric == World::getMassMatrix (dart/simulation/World.cpp:1974)
+ *   bias         [batch][num_dofs] output or NULL: C(q, v) with gravity, without
+ *                damping, spring or wrench == World::getCoriolisAndGravityForces
+ *                (World.cpp:1943)
+ * No snapshot, no LCP cache: the call reads its inputs and writes its outputs.
+ */
+int nimble_inverse_dynamics(nimble_world_t world, int32_t batch, const double* state,
+                            const double* ddq, const double* body_inertia,
+                            const double* body_wrench, int32_t wrench_frame, double* tau,
+                            double* mass_matrix, double* bias, void* stream);
+
+/*
+ * Vector-Jacobian product of nimble_inverse_dynamics with g = grad_tau
+ * [batch][num_dofs] (the transposed products of Skeleton::getJacobianOfID,
+ * dart/dynamics/Skeleton.cpp:1884, getJacobianOfC :1779 and the mass matrix,
+ * without forming any of them):
+ *   grad_state  [batch][2*num_dofs]  [(dID(q,v,a)/dq)^T g + K g,
+ *                                     (dC/dv)^T g + D g + dt K g]; the
+ *               derivative of -tau_ext with respect to q included (both frames)
+ *   grad_ddq    [batch][num_dofs]    M g
+ *   grad_wrench [batch][num_bodies][6] or NULL: minus the world twist of body b
+ *               under the rate vector g, in the frame of the input (wrench_frame
+ *               says which, also when body_wrench is NULL); there is no dt
+ * The same state, ddq, body_inertia, body_wrench and wrench_frame as the
+ * forward call.  Nothing is clipped to bounds.
+ */
+int nimble_inverse_dynamics_backward(nimble_world_t world, int32_t batch, const double* state,
+                                     const double* ddq, const double* body_inertia,
+                                     const double* body_wrench, int32_t wrench_frame,
+                                     const double* grad_tau, double* grad_state,
+                                     double* grad_ddq, double* grad_wrench, void* stream);
+
 /* Last error message (thread-local). */
 const char* nimble_last_error(void);
 

@@ -49,6 +49,22 @@ def _ext_prototypes():
 EXT_PROTOTYPES = _ext_prototypes()
 
 
+def _inverse_dynamics_prototypes():
+    """argtypes of the two inverse-dynamics entry points (include/nimble_amd.h):
+    world, batch, state, ddq, body_inertia, body_wrench, wrench_frame, then
+    the outputs (forward: tau, mass_matrix, bias; backward: grad_tau in,
+    grad_state, grad_ddq, grad_wrench out), the stream."""
+    v, i = C.c_void_p, C.c_int32
+    head = [v, i, v, v, v, v, i]
+    return {
+        "nimble_inverse_dynamics": head + [v, v, v] + [v],
+        "nimble_inverse_dynamics_backward": head + [v, v, v, v] + [v],
+    }
+
+
+ID_PROTOTYPES = _inverse_dynamics_prototypes()
+
+
 class NativeLibraryMissing(ImportError):
     pass
 
@@ -93,7 +109,7 @@ def lib():
             f = getattr(L, name)
             f.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * buffers + [C.c_void_p]
             f.restype = C.c_int
-        for name, argtypes in EXT_PROTOTYPES.items():
+        for name, argtypes in list(EXT_PROTOTYPES.items()) + list(ID_PROTOTYPES.items()):
             f = getattr(L, name)
             f.argtypes = argtypes
             f.restype = C.c_int
@@ -428,6 +444,57 @@ class DeviceWorld:
         else:
             _check(L.nimble_backward_inertia_ext(*head, _ptr(buffers[4]), *tail, stream))
         return None
+
+    def _id_args(self, state, ddq, body_inertia, body_wrench, wrench_frame, grad_wrench=None, **named):
+        """Checks shared by inverse_dynamics / inverse_dynamics_backward:
+        shapes, dtypes and the frame first (no device needed for those), then
+        that everything is on this world's device; `named` are further [B, n]
+        (or, by name, other) buffers.  Returns (B, frame flag)."""
+        n = self.n
+        if state.dim() != 2 or state.shape[1] != 2 * n:
+            raise ValueError(f"state shape {tuple(state.shape)} != (batch, {2 * n})")
+        B = state.shape[0]
+        want = {"mass_matrix": (B, n, n), "grad_state": (B, 2 * n)}
+        for name, t in (("state", state), ("ddq", ddq)) + tuple(named.items()):
+            if t is None:
+                continue
+            shape = want.get(name, (B, 2 * n) if name == "state" else (B, n))
+            if tuple(t.shape) != shape:
+                raise ValueError(f"{name} shape {tuple(t.shape)} != {shape}")
+            if str(t.dtype) != "torch.float64":
+                raise TypeError(f"{name} must be float64 (the reference's s_t); got {t.dtype}")
+            if not t.is_contiguous():
+                raise ValueError("nimblephysics_amd buffers must be contiguous")
+        self._inertia(B, body_inertia)
+        frame = self._wrench(B, body_wrench, wrench_frame, grad_wrench)
+        every = (state, ddq, body_inertia, body_wrench, grad_wrench) + tuple(named.values())
+        _require_device(*every)
+        self._on_my_device(*every)
+        return B, frame
+
+    def inverse_dynamics(self, state, ddq, tau, stream_ptr: int, body_inertia=None, body_wrench=None,
+                         wrench_frame="world", mass_matrix=None, bias=None):
+        """nimble_inverse_dynamics: tau [B, n] = M a + C - tau_ext + D v +
+        K (q - q0 + dt v) for state [B, 2n] and ddq [B, n]; `mass_matrix`
+        [B, n, n] and `bias` [B, n] (C with gravity alone) are filled when
+        given.  `body_inertia` / `body_wrench` / `wrench_frame` as for
+        forward()."""
+        B, frame = self._id_args(state, ddq, body_inertia, body_wrench, wrench_frame, tau=tau,
+                                 mass_matrix=mass_matrix, bias=bias)
+        _check(lib().nimble_inverse_dynamics(self.h, B, _ptr(state), _ptr(ddq), _ptr(body_inertia), _ptr(body_wrench),
+                                             frame, _ptr(tau), _ptr(mass_matrix), _ptr(bias),
+                                             C.c_void_p(stream_ptr)))
+
+    def inverse_dynamics_backward(self, state, ddq, grad_tau, grad_state, grad_ddq, stream_ptr: int,
+                                  body_inertia=None, body_wrench=None, wrench_frame="world", grad_wrench=None):
+        """nimble_inverse_dynamics_backward: the vector-Jacobian product with
+        grad_tau [B, n] into grad_state [B, 2n], grad_ddq [B, n] and (with
+        `body_wrench`) grad_wrench [B, num_bodies, 6], in the wrench's frame."""
+        B, frame = self._id_args(state, ddq, body_inertia, body_wrench, wrench_frame, grad_wrench,
+                                 grad_tau=grad_tau, grad_state=grad_state, grad_ddq=grad_ddq)
+        _check(lib().nimble_inverse_dynamics_backward(self.h, B, _ptr(state), _ptr(ddq), _ptr(body_inertia),
+                                                      _ptr(body_wrench), frame, _ptr(grad_tau), _ptr(grad_state),
+                                                      _ptr(grad_ddq), _ptr(grad_wrench), C.c_void_p(stream_ptr)))
 
     def jacobians(self, state, forces, snapshot, stream_ptr: int, body_inertia=None, body_wrench=None,
                   wrench_frame="world", wrench_jacobian=False):

@@ -50,6 +50,11 @@ struct nimble_world {
   // (the `_ext` kernels read every world's parameters from such blocks; with
   // the caller's body_inertia NULL they get this one, batch stride 0)
   double* inertiaDev = nullptr;
+  // the inverse-dynamics kernels (inverse_dynamics.cuh): their lean LDS
+  // layouts, and one zero [nb][6] block they read as every world's
+  // body_wrench (batch stride 0) when the caller gives none
+  Layout idFwd{}, idBwd{};
+  double* zeroWrenchDev = nullptr;
 };
 
 // body_wrench of an `_ext` call (nullptr: none), its frame flag, and the
@@ -103,6 +108,16 @@ extern "C" __global__ void nimble_backward_wide_ext_kernel(const ModelDev*, int,
                                                            double*, int, const double*, double*, double*, int, double*,
                                                            int, double*, int, int, int, const double*, int,
                                                            const double*, int, double*);
+
+// the inverse-dynamics kernels (inverse_dynamics.hip): their own layout by
+// value, per-world parameters and wrenches with their batch strides
+extern "C" __global__ void nimble_inverse_dynamics_kernel(const ModelDev*, Layout, const double*, const double*,
+                                                          const double*, int, const double*, int, int, double*,
+                                                          double*, double*);
+extern "C" __global__ void nimble_inverse_dynamics_backward_kernel(const ModelDev*, Layout, const double*,
+                                                                   const double*, const double*, int, const double*,
+                                                                   int, int, const double*, double*, double*,
+                                                                   double*);
 
 static void isoInverse(const double* T, double* O) {
   // [R|p]^-1 = [R^T | -R^T p]
@@ -179,6 +194,38 @@ static Layout makeLayout(const ModelDev& m, bool backward, int poolRows) {
       L.early = 1;
     take(area);
   }
+  L.total = o;
+  return L;
+}
+
+// The lean LDS layouts of the inverse-dynamics kernels: only the regions
+// their pieces of the step touch, every other offset -1.  Forward: state and
+// ddq (x), kinematics, packed M, the bias (rhs) and the dynamics buffers V, A,
+// IC, F (IC doubles as the accelerations' scratch, as in the step).
+// Backward: state, ddq (x), dL/dtau (w), kinematics, the adjoint vectors and
+// Wt, V, A, F -- no M and no composite inertias (M g comes from the adjoint
+// vectors); the accelerations' scratch (6n <= 36nb doubles) is the adjoint
+// area, not yet in use then.
+static Layout invDynLayout(const ModelDev& m, bool backward) {
+  Layout L;
+  std::memset(&L, 0xff, sizeof(L));  // every offset -1
+  int o = 0;
+  auto take = [&](int count) { int r = o; o += (count + 1) & ~1; return r; };
+  const int n = m.n, nb = m.nb;
+  L.q = take(n); L.v = take(n); L.x = take(n);
+  if (backward) L.w = take(n);
+  L.Tw = take(12 * nb); L.Sw = take(6 * n);
+  if (backward) {
+    L.adj = take(42 * nb); L.Wt = take(6 * nb);
+    L.IC = L.adj;
+    L.V = take(6 * nb); L.A = take(6 * nb); L.F = take(6 * nb);
+  } else {
+    L.M = take(n * (n + 1) / 2);
+    L.rhs = take(n);
+    L.V = take(6 * nb); L.A = take(6 * nb); L.IC = take(36 * nb); L.F = take(6 * nb);
+  }
+  L.poolCap = 0;
+  L.stage = 0; L.stageCap = 0;
   L.total = o;
   return L;
 }
@@ -513,6 +560,25 @@ int nimble_world_create(const nimble_world_desc* d, nimble_world_t* out) {
       return fail(NIMBLE_ERR_HIP, std::string("body parameters: ") + hipGetErrorString(e));
     }
   }
+  {
+    const std::vector<double> zero((size_t)m.nb * 6, 0.0);
+    e = hipMalloc(&w->zeroWrenchDev, zero.size() * sizeof(double));
+    if (e == hipSuccess)
+      e = hipMemcpy(w->zeroWrenchDev, zero.data(), zero.size() * sizeof(double), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+      if (w->zeroWrenchDev) (void)hipFree(w->zeroWrenchDev);
+      (void)hipFree(w->inertiaDev);
+      (void)hipFree(w->dev);
+      if (w->meshDev) (void)hipFree(w->meshDev);
+      delete w;
+      return fail(NIMBLE_ERR_HIP, std::string("zero wrench block: ") + hipGetErrorString(e));
+    }
+  }
+  w->idFwd = invDynLayout(m, false);
+  w->idBwd = invDynLayout(m, true);
+  if (getenv("NIMBLE_AMD_VERBOSE"))
+    fprintf(stderr, "nimble_amd: LDS inverse dynamics %d B, its backward %d B\n", w->idFwd.total * 8,
+            w->idBwd.total * 8);
   *out = w;
   return NIMBLE_OK;
 }
@@ -521,6 +587,7 @@ int nimble_world_destroy(nimble_world_t w) {
   if (!w) return NIMBLE_OK;
   if (w->dev) (void)hipFree(w->dev);
   if (w->inertiaDev) (void)hipFree(w->inertiaDev);
+  if (w->zeroWrenchDev) (void)hipFree(w->zeroWrenchDev);
   if (w->meshDev) (void)hipFree(w->meshDev);
   delete w;
   return NIMBLE_OK;
@@ -963,6 +1030,61 @@ static int fcJacobiansImpl(nimble_world_t w, int32_t batch, const double* state,
   HIP_TRY(launchBackward(w, grid, st, batch, state, forces, const_cast<double*>(snapshot), nullptr, dfc_dstate,
                         dfc_dforces, rows, w->jacWsDoubles > 0 ? workspace : nullptr, w->jacWsDoubles, nullptr, 1, 1,
                         body_inertia, ext));
+  return NIMBLE_OK;
+}
+
+// Inverse dynamics (inverse_dynamics.cuh): one workgroup per world, batches
+// beyond one launch's grid in chunks, as the forward.
+int nimble_inverse_dynamics(nimble_world_t w, int32_t batch, const double* state, const double* ddq,
+                            const double* body_inertia, const double* body_wrench, int32_t wrench_frame,
+                            double* tau, double* mass_matrix, double* bias, void* stream) {
+  if (!w || batch < 0) return fail(NIMBLE_ERR_INVALID, "bad arguments");
+  if (batch == 0 || w->host.n == 0) return NIMBLE_OK;
+  if (!state || !ddq || !tau) return fail(NIMBLE_ERR_INVALID, "null buffer");
+  if (body_wrench && badFrame(wrench_frame)) return fail(NIMBLE_ERR_INVALID, "bad wrench frame");
+  hipStream_t st = (hipStream_t)stream;
+  const size_t lds = (size_t)w->idFwd.total * sizeof(double);
+  const size_t n = (size_t)w->host.n, nb = (size_t)w->host.nb;
+  const int chunk = fwdChunk();
+  const int iStride = body_inertia ? (int)nb * 10 : 0, wStride = body_wrench ? (int)nb * 6 : 0;
+  for (int32_t b0 = 0; b0 < batch; b0 += chunk) {
+    const int cnt = batch - b0 < chunk ? batch - b0 : chunk;
+    hipLaunchKernelGGL(nimble_inverse_dynamics_kernel, dim3(cnt), dim3(64), lds, st, w->dev, w->idFwd,
+                       state + b0 * 2 * n, ddq + b0 * n,
+                       body_inertia ? body_inertia + b0 * nb * 10 : w->inertiaDev, iStride,
+                       body_wrench ? body_wrench + b0 * nb * 6 : w->zeroWrenchDev, wStride,
+                       body_wrench ? (int)wrench_frame : NIMBLE_WRENCH_WORLD, tau + b0 * n,
+                       mass_matrix ? mass_matrix + b0 * n * n : nullptr, bias ? bias + b0 * n : nullptr);
+    HIP_TRY(hipGetLastError());
+  }
+  return NIMBLE_OK;
+}
+
+int nimble_inverse_dynamics_backward(nimble_world_t w, int32_t batch, const double* state, const double* ddq,
+                                     const double* body_inertia, const double* body_wrench, int32_t wrench_frame,
+                                     const double* grad_tau, double* grad_state, double* grad_ddq,
+                                     double* grad_wrench, void* stream) {
+  if (!w || batch < 0) return fail(NIMBLE_ERR_INVALID, "bad arguments");
+  if (batch == 0 || w->host.n == 0) return NIMBLE_OK;
+  if (!state || !ddq || !grad_tau || !grad_state || !grad_ddq) return fail(NIMBLE_ERR_INVALID, "null buffer");
+  if ((body_wrench || grad_wrench) && badFrame(wrench_frame)) return fail(NIMBLE_ERR_INVALID, "bad wrench frame");
+  hipStream_t st = (hipStream_t)stream;
+  const size_t lds = (size_t)w->idBwd.total * sizeof(double);
+  const size_t n = (size_t)w->host.n, nb = (size_t)w->host.nb;
+  const int chunk = fwdChunk();
+  const int iStride = body_inertia ? (int)nb * 10 : 0, wStride = body_wrench ? (int)nb * 6 : 0;
+  // (the frame also says in which frame grad_wrench is wanted)
+  const int frame = body_wrench || grad_wrench ? (int)wrench_frame : NIMBLE_WRENCH_WORLD;
+  for (int32_t b0 = 0; b0 < batch; b0 += chunk) {
+    const int cnt = batch - b0 < chunk ? batch - b0 : chunk;
+    hipLaunchKernelGGL(nimble_inverse_dynamics_backward_kernel, dim3(cnt), dim3(64), lds, st, w->dev, w->idBwd,
+                       state + b0 * 2 * n, ddq + b0 * n,
+                       body_inertia ? body_inertia + b0 * nb * 10 : w->inertiaDev, iStride,
+                       body_wrench ? body_wrench + b0 * nb * 6 : w->zeroWrenchDev, wStride, frame,
+                       grad_tau + b0 * n, grad_state + b0 * 2 * n, grad_ddq + b0 * n,
+                       grad_wrench ? grad_wrench + b0 * nb * 6 : nullptr);
+    HIP_TRY(hipGetLastError());
+  }
   return NIMBLE_OK;
 }
 

@@ -42,23 +42,34 @@
 // external body wrenches (body_wrench, wrench.cuh; template parameter kExt).
 // A host build (the wavefront emulation of tests/cpp/wave_emu, one
 // translation unit with capi.cpp) has no code object to keep apart and takes
-// all sets.
+// all sets.  inverse_dynamics.hip (NIMBLE_INVERSE_DYNAMICS_KERNELS) takes none
+// of the step's thirteen kernels: only the two of inverse_dynamics.cuh, which
+// share the functions below with them.
 #if defined(NIMBLE_PER_WORLD_KERNELS)
 #define NIMBLE_SHARED_MODEL_INSTANCES 0
 #define NIMBLE_PER_WORLD_INSTANCES 1
 #define NIMBLE_EXT_WRENCH_INSTANCES 0
+#define NIMBLE_INVERSE_DYNAMICS_INSTANCES 0
 #elif defined(NIMBLE_EXT_WRENCH_KERNELS)
 #define NIMBLE_SHARED_MODEL_INSTANCES 0
 #define NIMBLE_PER_WORLD_INSTANCES 0
 #define NIMBLE_EXT_WRENCH_INSTANCES 1
+#define NIMBLE_INVERSE_DYNAMICS_INSTANCES 0
+#elif defined(NIMBLE_INVERSE_DYNAMICS_KERNELS)
+#define NIMBLE_SHARED_MODEL_INSTANCES 0
+#define NIMBLE_PER_WORLD_INSTANCES 0
+#define NIMBLE_EXT_WRENCH_INSTANCES 0
+#define NIMBLE_INVERSE_DYNAMICS_INSTANCES 1
 #elif defined(__HIP__)
 #define NIMBLE_SHARED_MODEL_INSTANCES 1
 #define NIMBLE_PER_WORLD_INSTANCES 0
 #define NIMBLE_EXT_WRENCH_INSTANCES 0
+#define NIMBLE_INVERSE_DYNAMICS_INSTANCES 0
 #else
 #define NIMBLE_SHARED_MODEL_INSTANCES 1
 #define NIMBLE_PER_WORLD_INSTANCES 1
 #define NIMBLE_EXT_WRENCH_INSTANCES 1
+#define NIMBLE_INVERSE_DYNAMICS_INSTANCES 1
 #endif
 
 // ---------------------------------------------------------------------------
@@ -1338,3 +1349,8 @@ nimble_backward_wide_ext_kernel(const ModelDev* __restrict__ mdp, int batch, con
                                wrenchFrame, gradWrench, inertiaStride);
 }
 #endif  // NIMBLE_EXT_WRENCH_INSTANCES
+
+#if NIMBLE_INVERSE_DYNAMICS_INSTANCES
+// nimble_inverse_dynamics_kernel and nimble_inverse_dynamics_backward_kernel
+#include "inverse_dynamics.cuh"
+#endif  // NIMBLE_INVERSE_DYNAMICS_INSTANCES

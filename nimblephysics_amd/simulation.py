@@ -590,6 +590,21 @@ class World:
         """d(next state)/d(action) [2n, |A|] at the current state (World.cpp:2227)."""
         return self.getCachedBackpropSnapshot().getActionJacobian(self)
 
+    # --- dynamics queries at the current state (inverse_dynamics.py) ----------
+    def getMassMatrix(self):
+        """World::getMassMatrix (World.cpp:1974): M(q) [n, n] at the world's
+        positions, over all of its dofs, from the device."""
+        import torch
+        from .inverse_dynamics import mass_matrix
+        return mass_matrix(self, torch.as_tensor(self.getPositions(), dtype=torch.float64)).numpy()
+
+    def getCoriolisAndGravityForces(self):
+        """World::getCoriolisAndGravityForces (World.cpp:1943): C(q, v) [n] with
+        gravity at the world's positions and velocities, from the device."""
+        import torch
+        from .inverse_dynamics import coriolis_and_gravity
+        return coriolis_and_gravity(self, torch.as_tensor(self.getState(), dtype=torch.float64)).numpy()
+
     # --- LCP warm start (BoxedLcpConstraintSolver::mX) ------------------------
     def setCachedLCPSolution(self, x):
         """World::setCachedLCPSolution (World.cpp): the warm start of the next
