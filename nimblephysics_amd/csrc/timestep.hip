@@ -533,7 +533,7 @@ __device__ __forceinline__ void forwardWorld(const ModelDev* __restrict__ mdp, c
       x[i] = s[L.tau + i] + springF + dampF - s[L.rhs + i];
     }
     WSYNC();
-    cholSolve(s + L.M, s + L.dinv, x, n, lane);  // x = ddq
+    cholSolve<true>(s + L.M, s + L.dinv, x, n, lane);  // x = ddq (the branchy form: chol_wave.cuh's note)
     // integrateVelocities (Skeleton.cpp:9329): v1 = v + dt ddq
     double* v1 = s + L.v1;
     for (int i = lane; i < n; i += WAVE) v1[i] = s[L.v + i] + md.dt * x[i];
