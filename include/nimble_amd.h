@@ -471,6 +471,43 @@ int nimble_inverse_dynamics_backward(nimble_world_t world, int32_t batch, const 
                                      const double* grad_tau, double* grad_state,
                                      double* grad_ddq, double* grad_wrench, void* stream);
 
+/*
+ * Batched contact inverse dynamics: which joint torques, and which wrenches on
+ * the named contact bodies, produce this motion of a floating-base skeleton
+ * whose six root dofs are not actuated?  == Skeleton::getContactInverseDynamics
+ * (dart/dynamics/Skeleton.cpp:9449, one contact body) and
+ * Skeleton::getMultipleContactInverseDynamics (Skeleton.cpp:9578), for a batch,
+ * in one launch.  With tau_full = nimble_inverse_dynamics(...) of the same
+ * inputs, r its six root rows r0 .. r0+5 and Jr [6k][6] the stacked
+ * body-frame Jacobians' root columns (the reference's jacBlock is Jr^T):
+ *   N = Jr^T diag(w) Jr,  y = N^-1 (r - Jr^T F0),  F = F0 + diag(w) Jr y,
+ *   tau = tau_full - J^T F, exactly 0.0 in the six root rows.
+ * With wrench_guesses F0 the weights w are 1: the solution nearest the
+ * guesses (the reference's KKT system, :9652-9664).  Without (NULL), F0 = 0
+ * and w = (1, 1, 1, 100, 100, 100) per body: the solution with the smallest
+ * moments (the reference's eps = 0.01 weighting :9643-9650 and its min-norm
+ * solve :9677); for one body the wrench is unique.  The dofs of other
+ * skeletons keep tau_full.  Contacts of the collision detector play no part.
+ *   state, ddq, body_inertia, body_wrench, wrench_frame   as for
+ *                    nimble_inverse_dynamics (body_wrench: known wrenches)
+ *   num_contact_bodies  k, 1 .. NIMBLE_MAX_CONTACT_BODIES
+ *   contact_bodies   [k] HOST array of device-model body indices: distinct,
+ *                    all of one skeleton whose root joint is NIMBLE_JOINT_FREE
+ *   wrench_guesses   [batch][k][6] device or NULL, body frame
+ *   tau              [batch][num_dofs]  output
+ *   contact_wrenches [batch][k][6]      output, [torque xyz, force xyz] in each
+ *                    contact body's own frame (NIMBLE_WRENCH_BODY)
+ * Not differentiable: pass contact_wrenches on to nimble_inverse_dynamics as
+ * a body-frame body_wrench for gradients.
+ */
+#define NIMBLE_MAX_CONTACT_BODIES 8
+int nimble_contact_inverse_dynamics(nimble_world_t world, int32_t batch, const double* state,
+                                    const double* ddq, const double* body_inertia,
+                                    const double* body_wrench, int32_t wrench_frame,
+                                    int32_t num_contact_bodies, const int32_t* contact_bodies,
+                                    const double* wrench_guesses, double* tau,
+                                    double* contact_wrenches, void* stream);
+
 /* Last error message (thread-local). */
 const char* nimble_last_error(void);
 

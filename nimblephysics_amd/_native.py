@@ -65,6 +65,18 @@ def _inverse_dynamics_prototypes():
 ID_PROTOTYPES = _inverse_dynamics_prototypes()
 
 
+def _contact_inverse_dynamics_prototypes():
+    """argtypes of nimble_contact_inverse_dynamics (include/nimble_amd.h): the
+    head of the inverse-dynamics entry points, then num_contact_bodies,
+    contact_bodies (host), wrench_guesses, tau, contact_wrenches, the stream."""
+    v, i = C.c_void_p, C.c_int32
+    return {"nimble_contact_inverse_dynamics": [v, i, v, v, v, v, i] + [i, v, v, v, v] + [v]}
+
+
+CID_PROTOTYPES = _contact_inverse_dynamics_prototypes()
+MAX_CONTACT_BODIES = 8  # NIMBLE_MAX_CONTACT_BODIES
+
+
 class NativeLibraryMissing(ImportError):
     pass
 
@@ -109,7 +121,8 @@ def lib():
             f = getattr(L, name)
             f.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * buffers + [C.c_void_p]
             f.restype = C.c_int
-        for name, argtypes in list(EXT_PROTOTYPES.items()) + list(ID_PROTOTYPES.items()):
+        for name, argtypes in (list(EXT_PROTOTYPES.items()) + list(ID_PROTOTYPES.items())
+                               + list(CID_PROTOTYPES.items())):
             f = getattr(L, name)
             f.argtypes = argtypes
             f.restype = C.c_int
@@ -495,6 +508,43 @@ class DeviceWorld:
         _check(lib().nimble_inverse_dynamics_backward(self.h, B, _ptr(state), _ptr(ddq), _ptr(body_inertia),
                                                       _ptr(body_wrench), frame, _ptr(grad_tau), _ptr(grad_state),
                                                       _ptr(grad_ddq), _ptr(grad_wrench), C.c_void_p(stream_ptr)))
+
+    def contact_inverse_dynamics(self, state, ddq, contact_bodies, tau, contact_wrenches, stream_ptr: int,
+                                 wrench_guesses=None, body_inertia=None, body_wrench=None, wrench_frame="world"):
+        """nimble_contact_inverse_dynamics: for state [B, 2n], ddq [B, n] and
+        the k device-model body indices `contact_bodies` (distinct, all of one
+        skeleton with a free root joint), tau [B, n] with the root's six rows
+        0 and contact_wrenches [B, k, 6] in each body's own frame;
+        `wrench_guesses` [B, k, 6] selects the solution nearest them.
+        `body_inertia` / `body_wrench` / `wrench_frame` as for
+        inverse_dynamics()."""
+        bodies = [int(b) for b in contact_bodies]
+        k = len(bodies)
+        if k < 1 or k > MAX_CONTACT_BODIES:
+            raise ValueError(f"{k} contact bodies: 1 .. {MAX_CONTACT_BODIES} are supported")
+        if min(bodies) < 0 or max(bodies) >= self.nb:
+            raise ValueError(f"contact body index outside 0 .. {self.nb - 1}: {bodies}")
+        if len(set(bodies)) != k:
+            raise ValueError(f"duplicate contact body: {bodies}")
+        if state.dim() != 2:
+            raise ValueError(f"state shape {tuple(state.shape)} != (batch, {2 * self.n})")
+        B = state.shape[0]
+        for name, t in (("contact_wrenches", contact_wrenches), ("wrench_guesses", wrench_guesses)):
+            if t is None:
+                continue
+            if tuple(t.shape) != (B, k, 6):
+                raise ValueError(f"{name} shape {tuple(t.shape)} != {(B, k, 6)}")
+            if str(t.dtype) != "torch.float64":
+                raise TypeError(f"{name} must be float64 (the reference's s_t); got {t.dtype}")
+            if not t.is_contiguous():
+                raise ValueError("nimblephysics_amd buffers must be contiguous")
+        _, frame = self._id_args(state, ddq, body_inertia, body_wrench, wrench_frame, tau=tau)
+        _require_device(contact_wrenches, wrench_guesses)
+        self._on_my_device(contact_wrenches, wrench_guesses)
+        idx = (C.c_int32 * k)(*bodies)
+        _check(lib().nimble_contact_inverse_dynamics(self.h, B, _ptr(state), _ptr(ddq), _ptr(body_inertia),
+                                                     _ptr(body_wrench), frame, k, idx, _ptr(wrench_guesses),
+                                                     _ptr(tau), _ptr(contact_wrenches), C.c_void_p(stream_ptr)))
 
     def jacobians(self, state, forces, snapshot, stream_ptr: int, body_inertia=None, body_wrench=None,
                   wrench_frame="world", wrench_jacobian=False):

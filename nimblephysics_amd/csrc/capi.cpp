@@ -119,6 +119,13 @@ extern "C" __global__ void nimble_inverse_dynamics_backward_kernel(const ModelDe
                                                                    int, int, const double*, double*, double*,
                                                                    double*);
 
+// the contact inverse-dynamics kernel (contact_inverse_dynamics.hip): the
+// inverse-dynamics forward's layout and its own arguments by value
+extern "C" __global__ void nimble_contact_inverse_dynamics_kernel(const ModelDev*, Layout, ContactIdArgs,
+                                                                  const double*, const double*, const double*, int,
+                                                                  const double*, int, int, const double*, double*,
+                                                                  double*);
+
 static void isoInverse(const double* T, double* O) {
   // [R|p]^-1 = [R^T | -R^T p]
   for (int r = 0; r < 3; r++)
@@ -228,6 +235,20 @@ static Layout invDynLayout(const ModelDev& m, bool backward) {
   L.stage = 0; L.stageCap = 0;
   L.total = o;
   return L;
+}
+
+// The LDS areas of the contact inverse-dynamics kernel behind the layout of
+// the inverse-dynamics forward (ContactIdArgs, model.h), for k contact bodies.
+static void contactIdAreas(const ModelDev& m, const Layout& L, int k, ContactIdArgs& P) {
+  int o = L.total;
+  auto take = [&](int count) { int r = o; o += (count + 1) & ~1; return r; };
+  P.Jr = take(36 * k);
+  P.N = take(21);
+  P.dinv = take(6);
+  P.y = take(6);
+  P.Fc = take(6 * k);
+  P.E = take(6 * m.nb);
+  P.total = o;
 }
 
 extern "C" {
@@ -1083,6 +1104,59 @@ int nimble_inverse_dynamics_backward(nimble_world_t w, int32_t batch, const doub
                        body_wrench ? body_wrench + b0 * nb * 6 : w->zeroWrenchDev, wStride, frame,
                        grad_tau + b0 * n, grad_state + b0 * 2 * n, grad_ddq + b0 * n,
                        grad_wrench ? grad_wrench + b0 * nb * 6 : nullptr);
+    HIP_TRY(hipGetLastError());
+  }
+  return NIMBLE_OK;
+}
+
+// Contact inverse dynamics (contact_inverse_dynamics.cuh): one workgroup per
+// world, one launch per chunk of the batch, as nimble_inverse_dynamics.
+int nimble_contact_inverse_dynamics(nimble_world_t w, int32_t batch, const double* state, const double* ddq,
+                                    const double* body_inertia, const double* body_wrench, int32_t wrench_frame,
+                                    int32_t num_contact_bodies, const int32_t* contact_bodies,
+                                    const double* wrench_guesses, double* tau, double* contact_wrenches,
+                                    void* stream) {
+  if (!w || batch < 0) return fail(NIMBLE_ERR_INVALID, "bad arguments");
+  const ModelDev& m = w->host;
+  const int k = num_contact_bodies;
+  if (k < 1 || k > NIMBLE_MAX_CONTACT_BODIES)
+    return fail(NIMBLE_ERR_INVALID, "num_contact_bodies must be 1 .. " + std::to_string(NIMBLE_MAX_CONTACT_BODIES));
+  if (!contact_bodies) return fail(NIMBLE_ERR_INVALID, "null contact_bodies");
+  ContactIdArgs P{};
+  P.k = k;
+  int root = -1;
+  for (int i = 0; i < k; i++) {
+    const int b = contact_bodies[i];
+    if (b < 0 || b >= m.nb) return fail(NIMBLE_ERR_INVALID, "contact body index out of range");
+    for (int j = 0; j < i; j++)
+      if (contact_bodies[j] == b) return fail(NIMBLE_ERR_INVALID, "duplicate contact body");
+    int r = b;
+    while (m.parent[r] >= 0) r = m.parent[r];
+    if (i > 0 && r != root) return fail(NIMBLE_ERR_INVALID, "contact bodies of different skeletons");
+    root = r;
+    P.bodies |= (unsigned long long)b << (8 * i);
+  }
+  if (m.jtype[root] != NIMBLE_JOINT_FREE)
+    return fail(NIMBLE_ERR_INVALID, "the contact bodies' root joint is not a free joint");
+  P.r0 = m.dof0[root];
+  if (body_wrench && badFrame(wrench_frame)) return fail(NIMBLE_ERR_INVALID, "bad wrench frame");
+  if (batch == 0) return NIMBLE_OK;
+  if (!state || !ddq || !tau || !contact_wrenches) return fail(NIMBLE_ERR_INVALID, "null buffer");
+  contactIdAreas(m, w->idFwd, k, P);
+  hipStream_t st = (hipStream_t)stream;
+  const size_t lds = (size_t)P.total * sizeof(double);
+  const size_t n = (size_t)m.n, nb = (size_t)m.nb;
+  const int chunk = fwdChunk();
+  const int iStride = body_inertia ? (int)nb * 10 : 0, wStride = body_wrench ? (int)nb * 6 : 0;
+  for (int32_t b0 = 0; b0 < batch; b0 += chunk) {
+    const int cnt = batch - b0 < chunk ? batch - b0 : chunk;
+    hipLaunchKernelGGL(nimble_contact_inverse_dynamics_kernel, dim3(cnt), dim3(64), lds, st, w->dev, w->idFwd, P,
+                       state + b0 * 2 * n, ddq + b0 * n,
+                       body_inertia ? body_inertia + b0 * nb * 10 : w->inertiaDev, iStride,
+                       body_wrench ? body_wrench + b0 * nb * 6 : w->zeroWrenchDev, wStride,
+                       body_wrench ? (int)wrench_frame : NIMBLE_WRENCH_WORLD,
+                       wrench_guesses ? wrench_guesses + (size_t)b0 * 6 * k : nullptr, tau + b0 * n,
+                       contact_wrenches + (size_t)b0 * 6 * k);
     HIP_TRY(hipGetLastError());
   }
   return NIMBLE_OK;

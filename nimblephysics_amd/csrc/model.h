@@ -119,3 +119,19 @@ struct ModelDev {
   Layout lay[2];
 };
 
+// Contact inverse dynamics (contact_inverse_dynamics.cuh): what its kernel
+// needs beyond the inverse-dynamics layout, passed by value as a kernel
+// argument of its own -- the k contact bodies (device-model indices < 256,
+// all of one skeleton whose root joint is free; body i in bits 8i .. 8i+7 of
+// `bodies`: a lane picks its body with a shift, where an array indexed by the
+// lane would be copied into per-lane scratch), the first of that root's six
+// dofs, and the LDS offsets (doubles) of its areas behind the layout's: Jr
+// [6k][6], packed N (21), dinv (6), y (6), the wrenches Fc [k][6] and the
+// world-frame wrenches E [nb][6]; total: the workgroup's LDS in doubles.
+struct ContactIdArgs {
+  int k, r0;
+  int Jr, N, dinv, y, Fc, E, total;
+  unsigned long long bodies;
+};
+static_assert(NIMBLE_MAX_CONTACT_BODIES == 8 && NIMBLE_MAX_BODIES <= 256, "ContactIdArgs::bodies holds 8 x 8 bits");
+

@@ -44,32 +44,45 @@
 // translation unit with capi.cpp) has no code object to keep apart and takes
 // all sets.  inverse_dynamics.hip (NIMBLE_INVERSE_DYNAMICS_KERNELS) takes none
 // of the step's thirteen kernels: only the two of inverse_dynamics.cuh, which
-// share the functions below with them.
+// share the functions below with them; contact_inverse_dynamics.hip
+// (NIMBLE_CONTACT_ID_KERNELS) likewise takes only the one kernel of
+// contact_inverse_dynamics.cuh.
 #if defined(NIMBLE_PER_WORLD_KERNELS)
 #define NIMBLE_SHARED_MODEL_INSTANCES 0
 #define NIMBLE_PER_WORLD_INSTANCES 1
 #define NIMBLE_EXT_WRENCH_INSTANCES 0
 #define NIMBLE_INVERSE_DYNAMICS_INSTANCES 0
+#define NIMBLE_CONTACT_ID_INSTANCES 0
 #elif defined(NIMBLE_EXT_WRENCH_KERNELS)
 #define NIMBLE_SHARED_MODEL_INSTANCES 0
 #define NIMBLE_PER_WORLD_INSTANCES 0
 #define NIMBLE_EXT_WRENCH_INSTANCES 1
 #define NIMBLE_INVERSE_DYNAMICS_INSTANCES 0
+#define NIMBLE_CONTACT_ID_INSTANCES 0
 #elif defined(NIMBLE_INVERSE_DYNAMICS_KERNELS)
 #define NIMBLE_SHARED_MODEL_INSTANCES 0
 #define NIMBLE_PER_WORLD_INSTANCES 0
 #define NIMBLE_EXT_WRENCH_INSTANCES 0
 #define NIMBLE_INVERSE_DYNAMICS_INSTANCES 1
+#define NIMBLE_CONTACT_ID_INSTANCES 0
+#elif defined(NIMBLE_CONTACT_ID_KERNELS)
+#define NIMBLE_SHARED_MODEL_INSTANCES 0
+#define NIMBLE_PER_WORLD_INSTANCES 0
+#define NIMBLE_EXT_WRENCH_INSTANCES 0
+#define NIMBLE_INVERSE_DYNAMICS_INSTANCES 0
+#define NIMBLE_CONTACT_ID_INSTANCES 1
 #elif defined(__HIP__)
 #define NIMBLE_SHARED_MODEL_INSTANCES 1
 #define NIMBLE_PER_WORLD_INSTANCES 0
 #define NIMBLE_EXT_WRENCH_INSTANCES 0
 #define NIMBLE_INVERSE_DYNAMICS_INSTANCES 0
+#define NIMBLE_CONTACT_ID_INSTANCES 0
 #else
 #define NIMBLE_SHARED_MODEL_INSTANCES 1
 #define NIMBLE_PER_WORLD_INSTANCES 1
 #define NIMBLE_EXT_WRENCH_INSTANCES 1
 #define NIMBLE_INVERSE_DYNAMICS_INSTANCES 1
+#define NIMBLE_CONTACT_ID_INSTANCES 1
 #endif
 
 // ---------------------------------------------------------------------------
@@ -1354,3 +1367,8 @@ nimble_backward_wide_ext_kernel(const ModelDev* __restrict__ mdp, int batch, con
 // nimble_inverse_dynamics_kernel and nimble_inverse_dynamics_backward_kernel
 #include "inverse_dynamics.cuh"
 #endif  // NIMBLE_INVERSE_DYNAMICS_INSTANCES
+
+#if NIMBLE_CONTACT_ID_INSTANCES
+// nimble_contact_inverse_dynamics_kernel
+#include "contact_inverse_dynamics.cuh"
+#endif  // NIMBLE_CONTACT_ID_INSTANCES

@@ -606,6 +606,30 @@ class Skeleton:
         for b in self.bodies:
             b.clearExternalForces()
 
+    # --- contact inverse dynamics (contact_inverse_dynamics.py) ----------------
+    def getContactInverseDynamics(self, accelerations, contactBody):
+        """Skeleton::getContactInverseDynamics (Skeleton.cpp:9449): the joint
+        torques and the one wrench on `contactBody` (its own frame) that give
+        this skeleton `accelerations` at the world's current positions and
+        velocities with the root left unactuated, from the device.  The
+        bodies' stored wrenches are applied."""
+        from .contact_inverse_dynamics import ContactInverseDynamicsResult, skeleton_contact_inverse_dynamics
+        pos, vel, acc, tau, F, ext = skeleton_contact_inverse_dynamics(self, accelerations, [contactBody], [])
+        return ContactInverseDynamicsResult(self, contactBody, pos, vel, acc, F[0], tau, ext)
+
+    def getMultipleContactInverseDynamics(self, accelerations, bodies, bodyWrenchGuesses=()):
+        """Skeleton::getMultipleContactInverseDynamics (Skeleton.cpp:9578):
+        likewise with a wrench on each of `bodies`; the solution nearest
+        `bodyWrenchGuesses` (one 6-vector per body, body frame) when given,
+        else the one with the smallest moments."""
+        from .contact_inverse_dynamics import MultipleContactInverseDynamicsResult, skeleton_contact_inverse_dynamics
+        bodies = list(bodies)
+        guesses = [np.asarray(g, dtype=np.float64).reshape(6) for g in bodyWrenchGuesses]
+        if guesses and len(guesses) != len(bodies):
+            raise ValueError(f"{len(guesses)} wrench guesses for {len(bodies)} bodies")
+        pos, vel, acc, tau, F, ext = skeleton_contact_inverse_dynamics(self, accelerations, bodies, guesses)
+        return MultipleContactInverseDynamicsResult(self, bodies, pos, vel, acc, list(F), guesses, tau, ext)
+
     def setMobile(self, mobile: bool):
         self.mobile = bool(mobile)
         _model_changed(self)
