@@ -472,6 +472,44 @@ int nimble_inverse_dynamics_backward(nimble_world_t world, int32_t batch, const 
                                      double* grad_ddq, double* grad_wrench, void* stream);
 
 /*
+ * nimble_inverse_dynamics_backward with one more output, the gradient in every
+ * body's inertial parameters (the transposed product of
+ * Skeleton::getJacobianOfID(ddq, wrt), dart/dynamics/Skeleton.cpp:1884, for wrt
+ * = GROUP_MASSES, GROUP_COMS and GROUP_INERTIAS, without forming the matrix):
+ *   grad_inertia [batch][num_bodies][10]  required; (d tau / d theta)^T g per
+ *                device-model body in INERTIA_FULL order (mass, local COM x y z,
+ *                Ixx Iyy Izz Ixy Ixz Iyz; dart/neural/WithRespectToMass.cpp:35),
+ *                the layout of body_inertia; every value is written, the rows
+ *                of the massless frames of compound-joint chains included
+ * tau is affine in a body's mass and moments and quadratic in its COM.
+ * Damping, springs, body_wrench (either frame) and dt do not enter.  The other
+ * arguments and outputs are those of nimble_inverse_dynamics_backward, to the
+ * bit; body_inertia, body_wrench and grad_wrench may be NULL as there.
+ */
+int nimble_invdyn_backward_inertia(nimble_world_t world, int32_t batch, const double* state,
+                                   const double* ddq, const double* body_inertia,
+                                   const double* body_wrench, int32_t wrench_frame,
+                                   const double* grad_tau, double* grad_state, double* grad_ddq,
+                                   double* grad_wrench, double* grad_inertia, void* stream);
+
+/*
+ * The Jacobian of nimble_inverse_dynamics in the inertial parameters ==
+ * Skeleton::getJacobianOfID(ddq, wrt) = getJacobianOfM(ddq, wrt) +
+ * getJacobianOfC(wrt) (dart/dynamics/Skeleton.cpp:1884, :1832, :1779) for wrt =
+ * GROUP_MASSES, GROUP_COMS and GROUP_INERTIAS at once, over all of the world's
+ * dofs and bodies, for a batch:
+ *   jacobian [batch][num_dofs][num_bodies][10]  required; d tau_j / d theta_{b,p},
+ *            p in INERTIA_FULL order as above.  Every element is written (the
+ *            memory may be uninitialised): exactly 0.0 where dof j is neither
+ *            body b's nor one of its ancestors'
+ * state, ddq and body_inertia (or NULL) as for nimble_inverse_dynamics; wrenches
+ * do not enter.
+ */
+int nimble_invdyn_inertia_jacobian(nimble_world_t world, int32_t batch, const double* state,
+                                   const double* ddq, const double* body_inertia, double* jacobian,
+                                   void* stream);
+
+/*
  * Batched contact inverse dynamics: which joint torques, and which wrenches on
  * the named contact bodies, produce this motion of a floating-base skeleton
  * whose six root dofs are not actuated?  == Skeleton::getContactInverseDynamics

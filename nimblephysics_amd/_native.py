@@ -65,6 +65,21 @@ def _inverse_dynamics_prototypes():
 ID_PROTOTYPES = _inverse_dynamics_prototypes()
 
 
+def _inverse_dynamics_inertia_prototypes():
+    """argtypes of the two entry points for the inertial parameters of the
+    inverse dynamics (include/nimble_amd.h): the backward's arguments with
+    grad_inertia ahead of the stream; world, batch, state, ddq, body_inertia,
+    jacobian, stream."""
+    v, i = C.c_void_p, C.c_int32
+    return {
+        "nimble_invdyn_backward_inertia": [v, i, v, v, v, v, i] + [v, v, v, v, v] + [v],
+        "nimble_invdyn_inertia_jacobian": [v, i, v, v, v, v] + [v],
+    }
+
+
+ID_INERTIA_PROTOTYPES = _inverse_dynamics_inertia_prototypes()
+
+
 def _contact_inverse_dynamics_prototypes():
     """argtypes of nimble_contact_inverse_dynamics (include/nimble_amd.h): the
     head of the inverse-dynamics entry points, then num_contact_bodies,
@@ -122,7 +137,7 @@ def lib():
             f.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * buffers + [C.c_void_p]
             f.restype = C.c_int
         for name, argtypes in (list(EXT_PROTOTYPES.items()) + list(ID_PROTOTYPES.items())
-                               + list(CID_PROTOTYPES.items())):
+                               + list(ID_INERTIA_PROTOTYPES.items()) + list(CID_PROTOTYPES.items())):
             f = getattr(L, name)
             f.argtypes = argtypes
             f.restype = C.c_int
@@ -467,7 +482,8 @@ class DeviceWorld:
         if state.dim() != 2 or state.shape[1] != 2 * n:
             raise ValueError(f"state shape {tuple(state.shape)} != (batch, {2 * n})")
         B = state.shape[0]
-        want = {"mass_matrix": (B, n, n), "grad_state": (B, 2 * n)}
+        want = {"mass_matrix": (B, n, n), "grad_state": (B, 2 * n), "grad_inertia": (B, self.nb, 10),
+                "jacobian": (B, n, self.nb, 10)}
         for name, t in (("state", state), ("ddq", ddq)) + tuple(named.items()):
             if t is None:
                 continue
@@ -499,15 +515,33 @@ class DeviceWorld:
                                              C.c_void_p(stream_ptr)))
 
     def inverse_dynamics_backward(self, state, ddq, grad_tau, grad_state, grad_ddq, stream_ptr: int,
-                                  body_inertia=None, body_wrench=None, wrench_frame="world", grad_wrench=None):
+                                  body_inertia=None, body_wrench=None, wrench_frame="world", grad_wrench=None,
+                                  grad_inertia=None):
         """nimble_inverse_dynamics_backward: the vector-Jacobian product with
         grad_tau [B, n] into grad_state [B, 2n], grad_ddq [B, n] and (with
-        `body_wrench`) grad_wrench [B, num_bodies, 6], in the wrench's frame."""
+        `body_wrench`) grad_wrench [B, num_bodies, 6], in the wrench's frame.
+        With `grad_inertia` [B, num_bodies, 10]
+        (nimble_invdyn_backward_inertia) also the gradient in every
+        device-model body's inertial parameters, INERTIA_FULL order."""
         B, frame = self._id_args(state, ddq, body_inertia, body_wrench, wrench_frame, grad_wrench,
-                                 grad_tau=grad_tau, grad_state=grad_state, grad_ddq=grad_ddq)
-        _check(lib().nimble_inverse_dynamics_backward(self.h, B, _ptr(state), _ptr(ddq), _ptr(body_inertia),
-                                                      _ptr(body_wrench), frame, _ptr(grad_tau), _ptr(grad_state),
-                                                      _ptr(grad_ddq), _ptr(grad_wrench), C.c_void_p(stream_ptr)))
+                                 grad_tau=grad_tau, grad_state=grad_state, grad_ddq=grad_ddq,
+                                 grad_inertia=grad_inertia)
+        head = (self.h, B, _ptr(state), _ptr(ddq), _ptr(body_inertia), _ptr(body_wrench), frame, _ptr(grad_tau),
+                _ptr(grad_state), _ptr(grad_ddq), _ptr(grad_wrench))
+        if grad_inertia is not None:
+            _check(lib().nimble_invdyn_backward_inertia(*head, _ptr(grad_inertia), C.c_void_p(stream_ptr)))
+        else:
+            _check(lib().nimble_inverse_dynamics_backward(*head, C.c_void_p(stream_ptr)))
+
+    def inverse_dynamics_inertia_jacobian(self, state, ddq, jacobian, stream_ptr: int, body_inertia=None):
+        """nimble_invdyn_inertia_jacobian: d tau / d theta into
+        `jacobian` [B, n, num_bodies, 10] (device-model bodies, INERTIA_FULL
+        order) for state [B, 2n] and ddq [B, n]; every element is written."""
+        if jacobian is None:
+            raise ValueError("jacobian is required")
+        B, _ = self._id_args(state, ddq, body_inertia, None, "world", jacobian=jacobian)
+        _check(lib().nimble_invdyn_inertia_jacobian(self.h, B, _ptr(state), _ptr(ddq), _ptr(body_inertia),
+                                                              _ptr(jacobian), C.c_void_p(stream_ptr)))
 
     def contact_inverse_dynamics(self, state, ddq, contact_bodies, tau, contact_wrenches, stream_ptr: int,
                                  wrench_guesses=None, body_inertia=None, body_wrench=None, wrench_frame="world"):

@@ -118,6 +118,15 @@ extern "C" __global__ void nimble_inverse_dynamics_backward_kernel(const ModelDe
                                                                    const double*, const double*, int, const double*,
                                                                    int, int, const double*, double*, double*,
                                                                    double*);
+// (the backward with grad_inertia behind grad_wrench; the Jacobian in the
+// inertial parameters: state, ddq, parameters, output)
+extern "C" __global__ void nimble_inverse_dynamics_backward_inertia_kernel(const ModelDev*, Layout, const double*,
+                                                                           const double*, const double*, int,
+                                                                           const double*, int, int, const double*,
+                                                                           double*, double*, double*, double*);
+extern "C" __global__ void nimble_inverse_dynamics_inertia_jacobian_kernel(const ModelDev*, Layout, const double*,
+                                                                           const double*, const double*, int,
+                                                                           double*);
 
 // the contact inverse-dynamics kernel (contact_inverse_dynamics.hip): the
 // inverse-dynamics forward's layout and its own arguments by value
@@ -1081,11 +1090,13 @@ int nimble_inverse_dynamics(nimble_world_t w, int32_t batch, const double* state
   return NIMBLE_OK;
 }
 
-int nimble_inverse_dynamics_backward(nimble_world_t w, int32_t batch, const double* state, const double* ddq,
-                                     const double* body_inertia, const double* body_wrench, int32_t wrench_frame,
-                                     const double* grad_tau, double* grad_state, double* grad_ddq,
-                                     double* grad_wrench, void* stream) {
-  if (!w || batch < 0) return fail(NIMBLE_ERR_INVALID, "bad arguments");
+// nimble_inverse_dynamics_backward (grad_inertia nullptr) and
+// nimble_invdyn_backward_inertia: the same launches, the second on
+// the kernel instance that also writes grad_inertia.
+static int invDynBackward(nimble_world_t w, int32_t batch, const double* state, const double* ddq,
+                          const double* body_inertia, const double* body_wrench, int32_t wrench_frame,
+                          const double* grad_tau, double* grad_state, double* grad_ddq, double* grad_wrench,
+                          double* grad_inertia, void* stream) {
   if (batch == 0 || w->host.n == 0) return NIMBLE_OK;
   if (!state || !ddq || !grad_tau || !grad_state || !grad_ddq) return fail(NIMBLE_ERR_INVALID, "null buffer");
   if ((body_wrench || grad_wrench) && badFrame(wrench_frame)) return fail(NIMBLE_ERR_INVALID, "bad wrench frame");
@@ -1098,12 +1109,61 @@ int nimble_inverse_dynamics_backward(nimble_world_t w, int32_t batch, const doub
   const int frame = body_wrench || grad_wrench ? (int)wrench_frame : NIMBLE_WRENCH_WORLD;
   for (int32_t b0 = 0; b0 < batch; b0 += chunk) {
     const int cnt = batch - b0 < chunk ? batch - b0 : chunk;
-    hipLaunchKernelGGL(nimble_inverse_dynamics_backward_kernel, dim3(cnt), dim3(64), lds, st, w->dev, w->idBwd,
-                       state + b0 * 2 * n, ddq + b0 * n,
+    const double* bi = body_inertia ? body_inertia + b0 * nb * 10 : w->inertiaDev;
+    const double* bw = body_wrench ? body_wrench + b0 * nb * 6 : w->zeroWrenchDev;
+    double* gw = grad_wrench ? grad_wrench + b0 * nb * 6 : nullptr;
+    if (grad_inertia)
+      hipLaunchKernelGGL(nimble_inverse_dynamics_backward_inertia_kernel, dim3(cnt), dim3(64), lds, st, w->dev,
+                         w->idBwd, state + b0 * 2 * n, ddq + b0 * n, bi, iStride, bw, wStride, frame,
+                         grad_tau + b0 * n, grad_state + b0 * 2 * n, grad_ddq + b0 * n, gw,
+                         grad_inertia + b0 * nb * 10);
+    else
+      hipLaunchKernelGGL(nimble_inverse_dynamics_backward_kernel, dim3(cnt), dim3(64), lds, st, w->dev, w->idBwd,
+                         state + b0 * 2 * n, ddq + b0 * n, bi, iStride, bw, wStride, frame, grad_tau + b0 * n,
+                         grad_state + b0 * 2 * n, grad_ddq + b0 * n, gw);
+    HIP_TRY(hipGetLastError());
+  }
+  return NIMBLE_OK;
+}
+
+int nimble_inverse_dynamics_backward(nimble_world_t w, int32_t batch, const double* state, const double* ddq,
+                                     const double* body_inertia, const double* body_wrench, int32_t wrench_frame,
+                                     const double* grad_tau, double* grad_state, double* grad_ddq,
+                                     double* grad_wrench, void* stream) {
+  if (!w || batch < 0) return fail(NIMBLE_ERR_INVALID, "bad arguments");
+  return invDynBackward(w, batch, state, ddq, body_inertia, body_wrench, wrench_frame, grad_tau, grad_state,
+                        grad_ddq, grad_wrench, nullptr, stream);
+}
+
+int nimble_invdyn_backward_inertia(nimble_world_t w, int32_t batch, const double* state, const double* ddq,
+                                   const double* body_inertia, const double* body_wrench, int32_t wrench_frame,
+                                   const double* grad_tau, double* grad_state, double* grad_ddq, double* grad_wrench,
+                                   double* grad_inertia, void* stream) {
+  if (!w || batch < 0) return fail(NIMBLE_ERR_INVALID, "bad arguments");
+  if (!grad_inertia) return fail(NIMBLE_ERR_INVALID, "null grad_inertia");
+  return invDynBackward(w, batch, state, ddq, body_inertia, body_wrench, wrench_frame, grad_tau, grad_state,
+                        grad_ddq, grad_wrench, grad_inertia, stream);
+}
+
+// The Jacobian of tau in the inertial parameters (inverse_dynamics.cuh
+// invDynInertiaJacobianWorld), on the forward's lean layout.
+int nimble_invdyn_inertia_jacobian(nimble_world_t w, int32_t batch, const double* state, const double* ddq,
+                                   const double* body_inertia, double* jacobian, void* stream) {
+  if (!w || batch < 0) return fail(NIMBLE_ERR_INVALID, "bad arguments");
+  if (!jacobian) return fail(NIMBLE_ERR_INVALID, "null jacobian");
+  if (batch == 0 || w->host.n == 0) return NIMBLE_OK;
+  if (!state || !ddq) return fail(NIMBLE_ERR_INVALID, "null buffer");
+  hipStream_t st = (hipStream_t)stream;
+  const size_t lds = (size_t)w->idFwd.total * sizeof(double);
+  const size_t n = (size_t)w->host.n, nb = (size_t)w->host.nb;
+  const int chunk = fwdChunk();
+  const int iStride = body_inertia ? (int)nb * 10 : 0;
+  for (int32_t b0 = 0; b0 < batch; b0 += chunk) {
+    const int cnt = batch - b0 < chunk ? batch - b0 : chunk;
+    hipLaunchKernelGGL(nimble_inverse_dynamics_inertia_jacobian_kernel, dim3(cnt), dim3(64), lds, st, w->dev,
+                       w->idFwd, state + b0 * 2 * n, ddq + b0 * n,
                        body_inertia ? body_inertia + b0 * nb * 10 : w->inertiaDev, iStride,
-                       body_wrench ? body_wrench + b0 * nb * 6 : w->zeroWrenchDev, wStride, frame,
-                       grad_tau + b0 * n, grad_state + b0 * 2 * n, grad_ddq + b0 * n,
-                       grad_wrench ? grad_wrench + b0 * nb * 6 : nullptr);
+                       jacobian + b0 * n * nb * 10);
     HIP_TRY(hipGetLastError());
   }
   return NIMBLE_OK;

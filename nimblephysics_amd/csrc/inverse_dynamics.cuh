@@ -18,7 +18,14 @@
 // the model's own parameters come as one [nb][10] block with batch stride 0,
 // absent wrenches as one zero [nb][6] block with batch stride 0 (every world
 // reads the same cached lines).
+//
+// The inertial parameters (inertia_grad.cuh): the backward's kInertia
+// instance, nimble_inverse_dynamics_backward_inertia_kernel, adds gradInertia
+// = (d tau / d theta)^T g, and nimble_inverse_dynamics_inertia_jacobian_kernel
+// writes the matrix d tau / d theta itself.
 #pragma once
+
+#include "inertia_grad.cuh"
 
 // Body forces without the wrench at the accelerations in L.A, summed over the
 // subtrees into L.F: f_b = I_b (A_b - a_g) + V_b x* (I_b V_b), the forces of
@@ -117,6 +124,14 @@ __device__ __forceinline__ void invDynWorld(const ModelDev* __restrict__ mdp, co
 // dof's body.  The kinematics are computed here (the step's backward reloads
 // them from its snapshot); the per-dof columns are restated from
 // backwardItems, which stays as it is.
+// kInertia: one more output,
+//   gradInertia[b][p] = W_b . phi_{b,p}    [B][nb][10], INERTIA_FULL order
+// with W_b = sum of S_j g_j over the dofs of b and of its ancestors (the Wt of
+// adjointVectors) and phi_{b,p} the derivative of the body's force with
+// respect to its parameter p (inertia_grad.cuh): lane = body, all ten values
+// of every device-model body, the massless frames of compound-joint chains
+// included.  Damping, springs, the wrenches and dt do not enter.
+template <bool kInertia = false>
 __device__ __forceinline__ void invDynBackwardWorld(const ModelDev* __restrict__ mdp, const Layout& L,
                                                     const double* __restrict__ state,
                                                     const double* __restrict__ ddq,
@@ -124,7 +139,8 @@ __device__ __forceinline__ void invDynBackwardWorld(const ModelDev* __restrict__
                                                     const double* __restrict__ bodyWrench, int wrenchStride,
                                                     int wrenchFrame, const double* __restrict__ gradTau,
                                                     double* __restrict__ gradState, double* __restrict__ gradDdq,
-                                                    double* __restrict__ gradWrench) {
+                                                    double* __restrict__ gradWrench,
+                                                    double* __restrict__ gradInertia = nullptr) {
   extern __shared__ double s[];
   const ModelDev& md = *mdp;
   const int lane = threadIdx.x;
@@ -152,6 +168,19 @@ __device__ __forceinline__ void invDynBackwardWorld(const ModelDev* __restrict__
     for (int i = 0; i < 6; i++) Wd[i] = -s[L.Wt + 6 * b + i];
     twistInWrenchFrame(Wd, wrenchFrame, s + L.Tw + 12 * b, gw);
     for (int i = 0; i < 6; i++) gradWrench[((size_t)env * md.nb + b) * 6 + i] = gw[i];
+  }
+  if constexpr (kInertia) {
+    if (lane < md.nb) {
+      const int b = lane;
+      const double* bi = bodyInertia + (size_t)env * inertiaStride + 10 * b;
+      const double ag[6] = {0, 0, 0, md.g[0], md.g[1], md.g[2]};
+      double u[6];
+      for (int i = 0; i < 6; i++) u[i] = s[L.A + 6 * b + i] - ag[i];
+      double* gi = gradInertia + ((size_t)env * md.nb + b) * 10;
+#pragma unroll
+      for (int p = 0; p < 10; p++)
+        gi[p] = inertiaPhiDot(s + L.Tw + 12 * b, bi[0], bi + 1, s + L.V + 6 * b, u, s + L.Wt + 6 * b, p);
+    }
   }
   const int k = lane;
   if (k < n) {
@@ -206,6 +235,54 @@ __device__ __forceinline__ void invDynBackwardWorld(const ModelDev* __restrict__
   }
 }
 
+// jacobian [B][n][nb][10]: d tau_j / d theta_{b,p} = S_j . phi_{b,p} where dof
+// j belongs to body b or to one of its ancestors, exactly 0.0 elsewhere --
+// Skeleton::getJacobianOfID(ddq, wrt) = getJacobianOfM(ddq, wrt) +
+// getJacobianOfC(wrt) (Skeleton.cpp:1884, :1832, :1779) for wrt = GROUP_MASSES,
+// GROUP_COMS and GROUP_INERTIAS at once, over all of the world's bodies.  Only
+// the kinematics with ddq = a run (Tw, Sw, V, A on the forward's lean layout;
+// no composites, no M).  One lane per element, in the order of the output:
+// neighbouring lanes store neighbouring addresses, every element is written
+// (the caller's memory may be uninitialised), and a lane holds one value of
+// one parameter at a time, never a body's ten 6-vectors phi.
+__device__ __forceinline__ void invDynInertiaJacobianWorld(const ModelDev* __restrict__ mdp, const Layout& L,
+                                                           const double* __restrict__ state,
+                                                           const double* __restrict__ ddq,
+                                                           const double* __restrict__ bodyInertia,
+                                                           int inertiaStride, double* __restrict__ jacobian) {
+  extern __shared__ double s[];
+  const ModelDev& md = *mdp;
+  const int lane = threadIdx.x;
+  const int n = md.n;
+  const int env = blockIdx.x;
+  {
+    const double* st = state + (size_t)env * 2 * n;
+    const double* a = ddq + (size_t)env * n;
+    for (int i = lane; i < n; i += WAVE) {
+      s[L.q + i] = st[i];
+      s[L.v + i] = st[n + i];
+      s[L.x + i] = a[i];
+    }
+    WSYNC();
+  }
+  kinematics(md, s, L, lane, s + L.x);
+  const double* bi = bodyInertia + (size_t)env * inertiaStride;
+  const double ag[6] = {0, 0, 0, md.g[0], md.g[1], md.g[2]};
+  const int row = 10 * md.nb, total = n * row;
+  double* J = jacobian + (size_t)env * total;
+  for (int t = lane; t < total; t += WAVE) {
+    const int j = t / row, r = t - j * row;
+    const int b = r / 10, p = r - 10 * b;
+    double val = 0.0;
+    if ((md.anc[b] >> md.dofBody[j]) & 1ull) {
+      double u[6];
+      for (int i = 0; i < 6; i++) u[i] = s[L.A + 6 * b + i] - ag[i];
+      val = inertiaPhiDot(s + L.Tw + 12 * b, bi[10 * b], bi + 10 * b + 1, s + L.V + 6 * b, u, s + L.Sw + 6 * j, p);
+    }
+    J[t] = val;
+  }
+}
+
 // (the kernels: the workgroup's dynamic LDS is declared in the functions
 // above, as in the step's kernels)
 extern "C" __global__ void __launch_bounds__(WAVE)
@@ -225,6 +302,26 @@ nimble_inverse_dynamics_backward_kernel(const ModelDev* __restrict__ mdp, Layout
                                         int wrenchFrame, const double* __restrict__ gradTau,
                                         double* __restrict__ gradState, double* __restrict__ gradDdq,
                                         double* __restrict__ gradWrench) {
-  invDynBackwardWorld(mdp, L, state, ddq, bodyInertia, inertiaStride, bodyWrench, wrenchStride, wrenchFrame, gradTau,
-                      gradState, gradDdq, gradWrench);
+  invDynBackwardWorld<false>(mdp, L, state, ddq, bodyInertia, inertiaStride, bodyWrench, wrenchStride, wrenchFrame,
+                             gradTau, gradState, gradDdq, gradWrench);
+}
+
+extern "C" __global__ void __launch_bounds__(WAVE)
+nimble_inverse_dynamics_backward_inertia_kernel(const ModelDev* __restrict__ mdp, Layout L,
+                                                const double* __restrict__ state, const double* __restrict__ ddq,
+                                                const double* __restrict__ bodyInertia, int inertiaStride,
+                                                const double* __restrict__ bodyWrench, int wrenchStride,
+                                                int wrenchFrame, const double* __restrict__ gradTau,
+                                                double* __restrict__ gradState, double* __restrict__ gradDdq,
+                                                double* __restrict__ gradWrench, double* __restrict__ gradInertia) {
+  invDynBackwardWorld<true>(mdp, L, state, ddq, bodyInertia, inertiaStride, bodyWrench, wrenchStride, wrenchFrame,
+                            gradTau, gradState, gradDdq, gradWrench, gradInertia);
+}
+
+extern "C" __global__ void __launch_bounds__(WAVE)
+nimble_inverse_dynamics_inertia_jacobian_kernel(const ModelDev* __restrict__ mdp, Layout L,
+                                                const double* __restrict__ state, const double* __restrict__ ddq,
+                                                const double* __restrict__ bodyInertia, int inertiaStride,
+                                                double* __restrict__ jacobian) {
+  invDynInertiaJacobianWorld(mdp, L, state, ddq, bodyInertia, inertiaStride, jacobian);
 }

@@ -43,7 +43,7 @@
 // A host build (the wavefront emulation of tests/cpp/wave_emu, one
 // translation unit with capi.cpp) has no code object to keep apart and takes
 // all sets.  inverse_dynamics.hip (NIMBLE_INVERSE_DYNAMICS_KERNELS) takes none
-// of the step's thirteen kernels: only the two of inverse_dynamics.cuh, which
+// of the step's thirteen kernels: only those of inverse_dynamics.cuh, which
 // share the functions below with them; contact_inverse_dynamics.hip
 // (NIMBLE_CONTACT_ID_KERNELS) likewise takes only the one kernel of
 // contact_inverse_dynamics.cuh.

@@ -30,11 +30,29 @@ differentiable here: a ``mass`` that requires grad raises.  ``body_wrench``
 and ``wrench_frame`` as in ``timestep``; the stored wrenches of the world's
 bodies are not applied.
 
+``body_inertia`` (instead of ``mass``): every body's ten inertial parameters
+in INERTIA_FULL order (mass, local COM x y z, Ixx Iyy Izz Ixy Ixz Iyz), one
+row per body in the world's body order (the order of ``body_wrench``):
+[nBodies, 10], shared by the batch, or [B, nBodies, 10], one set per world.
+It is differentiable; the gradient of a shared set is summed over the batch.
+For a tuned mass vector: ``body_inertia=world.getBodyInertiaParameters(mass)``,
+which autograd follows back to ``mass``.
+
 Gradients (nimble_inverse_dynamics_backward), with g = dL/dtau:
     d/d ddq         M g
     d/d state       [(dID(q,v,a)/dq)^T g + K g,  (dC/dv)^T g + D g + dt K g]
     d/d body_wrench minus the world twist of body b under the rate vector g,
                     in the frame of the input
+    d/d body_inertia (d tau / d theta)^T g
+                    (nimble_invdyn_backward_inertia; the transposed
+                    Skeleton::getJacobianOfID(ddq, wrt), Skeleton.cpp:1884, for
+                    wrt = GROUP_MASSES, GROUP_COMS, GROUP_INERTIAS)
+
+``inverse_dynamics_inertia_jacobian(world, state, ddq)`` is that matrix itself,
+d tau / d theta [.., n, nBodies, 10] (getJacobianOfM + getJacobianOfC,
+Skeleton.cpp:1832, :1779), for Gauss-Newton and least-squares fits of the
+parameters; tau is affine in a body's mass and moments and quadratic in its
+COM.  Not differentiable.
 
 ``mass_matrix(world, q)`` [.., n, n] and ``coriolis_and_gravity(world, state)``
 [.., n] are World::getMassMatrix (dart/simulation/World.cpp:1974) and
@@ -69,6 +87,30 @@ def _body_inertia(world: World, mass: Optional[torch.Tensor], B: int, cdev):
     return world._batched_inertia(mass.detach().to(cdev, torch.float64).contiguous())
 
 
+def _body_inertia_shared(world: World, body_inertia: torch.Tensor, state: torch.Tensor) -> bool:
+    """Checks the shape of `body_inertia` for this state (before anything
+    touches a device); True when it is one set [nBodies, 10] for the batch."""
+    nbw = world.getNumBodyNodes()
+    shape = tuple(body_inertia.shape)
+    shared = body_inertia.dim() == 2
+    if shape[-2:] != (nbw, 10) or body_inertia.dim() not in (2, 3) or (state.dim() == 1 and not shared):
+        want = f"[{nbw}, 10]" if state.dim() == 1 else f"[{nbw}, 10] or [{state.shape[0]}, {nbw}, 10]"
+        raise ValueError(f"body_inertia must be {want} for this state (INERTIA_FULL order per body of the world), "
+                         f"got {shape}")
+    if not shared and shape[0] != state.shape[0]:
+        raise ValueError(f"per-world body_inertia must be [{state.shape[0]}, {nbw}, 10] for this state, got {shape}")
+    return shared
+
+
+def _stage_body_inertia(world: World, body_inertia: torch.Tensor, shared: bool, B: int, cdev):
+    """The kernels' per-world parameter array [B, num_bodies, 10] for
+    `body_inertia` in the world's body order."""
+    p = body_inertia.detach().to(cdev, torch.float64)
+    if shared:
+        p = p.unsqueeze(0).expand(B, *p.shape)
+    return world._scatter_inertia(p).contiguous()
+
+
 def _stage(world: World, state: torch.Tensor, ddq: Optional[torch.Tensor], cdev):
     """2-D contiguous float64 device copies of state (and ddq)."""
     n = world.getNumDofs()
@@ -91,10 +133,13 @@ def _stage(world: World, state: torch.Tensor, ddq: Optional[torch.Tensor], cdev)
 class InverseDynamicsLayer(torch.autograd.Function):
     @staticmethod
     def forward(ctx, world: World, state: torch.Tensor, ddq: torch.Tensor, mass: Optional[torch.Tensor],
-                body_wrench: Optional[torch.Tensor] = None, wrench_frame="world"):
+                body_wrench: Optional[torch.Tensor] = None, wrench_frame="world",
+                body_inertia: Optional[torch.Tensor] = None):
+        if mass is not None and body_inertia is not None:
+            raise ValueError("inverse_dynamics: give mass or body_inertia, not both")
         if mass is not None and mass.requires_grad:
-            raise ValueError("inverse_dynamics: mass is not differentiable here (detach it, or differentiate through "
-                             "timestep)")
+            raise ValueError("inverse_dynamics: mass is not differentiable here (detach it, pass "
+                             "body_inertia=world.getBodyInertiaParameters(mass), or differentiate through timestep)")
         frame = wrench_frame_flag(wrench_frame)
         if body_wrench is not None:
             want = (world.getNumBodyNodes(), 6) if state.dim() == 1 else (state.shape[0], world.getNumBodyNodes(), 6)
@@ -102,12 +147,18 @@ class InverseDynamicsLayer(torch.autograd.Function):
                 raise ValueError(f"body_wrench must be {list(want)} for this state ([torque xyz, force xyz] per body "
                                  f"of the world), got {tuple(body_wrench.shape)}")
             ctx.wrench_device = body_wrench.device
+        ctx.inertia_shared = False
+        if body_inertia is not None:
+            ctx.inertia_shared = _body_inertia_shared(world, body_inertia, state)
+            ctx.inertia_device = body_inertia.device
         ctx.out_device = state.device
         cdev = _compute_device(state)
         with torch.cuda.device(cdev):
             squeeze, st, a = _stage(world, state, ddq, cdev)
             B = st.shape[0]
             bi = _body_inertia(world, mass, B, cdev)
+            if body_inertia is not None:
+                bi = _stage_body_inertia(world, body_inertia, ctx.inertia_shared, B, cdev)
             bw = None
             if body_wrench is not None:
                 w3 = body_wrench.detach().to(cdev, torch.float64)
@@ -137,23 +188,58 @@ class InverseDynamicsLayer(torch.autograd.Function):
             ga = torch.empty_like(a)
             bw = ctx.body_wrench
             gw = torch.empty_like(bw) if bw is not None and ctx.needs_input_grad[4] else None
+            # (a body_inertia that does not require grad: the entry point without grad_inertia)
+            gi = torch.empty_like(ctx.body_inertia) if ctx.needs_input_grad[6] else None
             stream = torch.cuda.current_stream(st.device).cuda_stream
             dev.inverse_dynamics_backward(st, a, g, gs, ga, stream, body_inertia=ctx.body_inertia, body_wrench=bw,
-                                          wrench_frame=ctx.wrench_frame, grad_wrench=gw)
+                                          wrench_frame=ctx.wrench_frame, grad_wrench=gw, grad_inertia=gi)
         od = ctx.out_device
         if gw is not None:
             gw = ctx.world._gather_wrench(gw)
             gw = (gw[0] if ctx.squeeze else gw).to(ctx.wrench_device)
+        if gi is not None:
+            gi = ctx.world._gather_inertia(gi)
+            gi = (gi.sum(0) if ctx.inertia_shared else gi).to(ctx.inertia_device)
         if ctx.squeeze:
-            return None, gs[0].to(od), ga[0].to(od), None, gw, None
-        return None, gs.to(od), ga.to(od), None, gw, None
+            return None, gs[0].to(od), ga[0].to(od), None, gw, None, gi
+        return None, gs.to(od), ga.to(od), None, gw, None, gi
 
 
 def inverse_dynamics(world: World, state: torch.Tensor, ddq: torch.Tensor, mass: Optional[torch.Tensor] = None,
-                     body_wrench: Optional[torch.Tensor] = None, wrench_frame="world") -> torch.Tensor:
-    """tau = ID(q, v, a), differentiable in state, ddq and body_wrench; see the
-    module docstring."""
-    return InverseDynamicsLayer.apply(world, state, ddq, mass, body_wrench, wrench_frame)
+                     body_wrench: Optional[torch.Tensor] = None, wrench_frame="world",
+                     body_inertia: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """tau = ID(q, v, a), differentiable in state, ddq, body_wrench and
+    body_inertia; see the module docstring."""
+    return InverseDynamicsLayer.apply(world, state, ddq, mass, body_wrench, wrench_frame, body_inertia)
+
+
+def inverse_dynamics_inertia_jacobian(world: World, state: torch.Tensor, ddq: torch.Tensor,
+                                      body_inertia: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """d tau / d theta: [n, nBodies, 10] for a 1-D state, [B, n, nBodies, 10]
+    for [B, 2n]; bodies in the world's body order, parameters in INERTIA_FULL
+    order (Skeleton::getJacobianOfID(ddq, wrt), Skeleton.cpp:1884, for wrt =
+    GROUP_MASSES, GROUP_COMS and GROUP_INERTIAS, for a batch).  body_inertia
+    as in inverse_dynamics.  Exactly 0 where the dof is neither the body's nor
+    one of its ancestors'.  Not differentiable."""
+    n = world.getNumDofs()
+    if state.dim() not in (1, 2) or state.shape[-1] != 2 * n:
+        raise ValueError(f"state has {state.shape[-1]} columns, world expects {2 * n}")
+    if ddq.dim() != state.dim() or tuple(ddq.shape) != tuple(state.shape[:-1]) + (n,):
+        raise ValueError(f"ddq must be {list(state.shape[:-1]) + [n]} for this state, got {list(ddq.shape)}")
+    shared = body_inertia is not None and _body_inertia_shared(world, body_inertia, state)
+    out_device = state.device
+    cdev = _compute_device(state)
+    with torch.cuda.device(cdev):
+        squeeze, st, a = _stage(world, state, ddq, cdev)
+        B = st.shape[0]
+        bi = None
+        if body_inertia is not None:
+            bi = _stage_body_inertia(world, body_inertia, shared, B, cdev)
+        dev = world.native(cdev)
+        J = torch.empty((B, n, dev.nb, 10), dtype=torch.float64, device=cdev)
+        dev.inverse_dynamics_inertia_jacobian(st, a, J, torch.cuda.current_stream(cdev).cuda_stream, body_inertia=bi)
+        J = world._gather_inertia(J)
+    return (J[0] if squeeze else J).to(out_device)
 
 
 def _queries(world: World, state: torch.Tensor, want_mass: bool, want_bias: bool):

@@ -356,6 +356,61 @@ class World:
             out[:, rows] = mass2d.detach().to(torch.float64).index_select(1, cols) * coef
         return out.reshape(B, -1, 10)
 
+    def getBodyInertiaParameters(self, mass=None):
+        """Every body's ten inertial parameters in INERTIA_FULL order (mass,
+        local COM x y z, Ixx Iyy Izz Ixy Ixz Iyz), one row per body in the
+        world's body order (skeleton by skeleton, getNumBodyNodes() rows, the
+        order of ``body_wrench``): the ``body_inertia`` of inverse_dynamics.
+        ``mass`` None: the bodies' own values, [nBodies, 10].  A 1-D ``mass``
+        (the world's getMassDims() tuned values): the same with the tuned
+        components replaced, [nBodies, 10]; 2-D [B, getMassDims()]: one set
+        per world, [B, nBodies, 10].  The values are _batched_inertia()'s, on
+        the device of ``mass``, put together with torch operations that
+        autograd follows: the gradient reaches ``mass`` through
+        _mass_selection()'s plan (an INERTIA_COM_MU entry with its beta
+        factors; where two entries tune one component the later entry has the
+        value and the gradient).  The world's bodies are not touched."""
+        import torch
+        rows = torch.as_tensor(self._wrench_device_rows(), dtype=torch.long)
+        if mass is None:
+            return torch.as_tensor(self._body_inertia_base(), dtype=torch.float64).index_select(0, rows)
+        D = self.getMassDims()
+        if mass.dim() not in (1, 2) or mass.shape[-1] != D:
+            raise ValueError(f"mass must be [{D}] or [batch, {D}] (the world's tuned mass dims), got "
+                             f"{tuple(mass.shape)}")
+        m2 = (mass.reshape(1, D) if mass.dim() == 1 else mass).to(torch.float64)
+        values = self._batched_inertia(m2.detach())  # (and the plan for this device)
+        _, _, prow, pcol, coef = self._batched_inertia_plan
+        flat = values.reshape(m2.shape[0], -1)
+        if prow.numel() > 0:
+            flat = flat.index_copy(1, prow, m2.index_select(1, pcol) * coef)
+        out = flat.reshape(m2.shape[0], -1, 10).index_select(1, rows.to(m2.device))
+        return out[0] if mass.dim() == 1 else out
+
+    def _scatter_inertia(self, params):
+        """[B, getNumBodyNodes(), 10] parameter rows in the world's body order
+        -> the kernels' body_inertia [B, num_bodies, 10] in device-model order
+        (as _scatter_wrench); chain frames get zero rows."""
+        import torch
+        nbw = self.getNumBodyNodes()
+        if params.dim() != 3 or tuple(params.shape[1:]) != (nbw, 10):
+            raise ValueError(f"body_inertia must be [batch, {nbw}, 10] (the world's bodies, INERTIA_FULL order), got "
+                             f"{tuple(params.shape)}")
+        rows = self._wrench_device_rows()
+        nb = len(self._model_bodies())
+        p = params.detach().to(torch.float64)
+        if nb == nbw:
+            return p.contiguous()
+        out = torch.zeros((p.shape[0], nb, 10), dtype=torch.float64, device=p.device)
+        out.index_copy_(1, torch.as_tensor(rows, dtype=torch.long).to(p.device), p)
+        return out
+
+    def _gather_inertia(self, dev_params):
+        """The inverse selection (as _gather_wrench): the rows of a
+        device-order [..., num_bodies, 10] array for the world's bodies; the
+        chain frames' rows are dropped."""
+        return self._gather_wrench(dev_params)
+
     # --- external body wrenches (see timestep.py) -----------------------------
     def _world_bodies(self):
         """Every BodyNode in the world's body order: skeleton by skeleton,
